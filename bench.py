@@ -11,14 +11,24 @@ configs[2] instead (MvNormal, full 2048 x 2048 covariance; cache-resident).
 A "step" is one NUTS draw.  `--warmup W` tuning draws run untimed, then EXACTLY
 `--steps K` post-warmup draws are timed between barrier + device synchronisation.
 
+A plain run does only what the headline needs: set-up, the W warmup draws, the K
+timed draws, and the one JSON line.  `--full` adds the legs that are not the
+headline: the separate ESS run (`ess_run`) when K or W is too short for an ESS, the
+CPU baseline, C3's chains on one GPU, and the oracle's own chains of this shape
+(`oracle_convergence`).  `--dump-outputs DIR` writes what the last timed step
+returned -- its draw and its sampler statistics -- as DIR/<name>.npy (float64); the
+data and the seeds depend only on the arguments, so two builds can be compared
+output for output.
+
 value: BASELINE.json's metric names two numbers, effective samples/sec and leapfrog
 steps/sec.  Effective samples/sec = sum over chains of the min-over-ALL-parameters
 bulk-ESS of the K timed draws / max-over-ranks wall time -- it is only an estimate of
 anything when the chain is tuned and K is a few hundred draws, so it is `value` when
 K >= 200 and W >= 200; for shorter runs (e.g. a driver smoke run with K = 20) `value`
 is the aggregate leapfrog steps/sec and the ESS fields are null (`value_is` says
-which).  `convergence` carries max R-hat, min / median ESS and WHICH parameter has
-the minimum, so a small min-ESS can be traced to the coordinate that does not mix.
+which; `--full` fills them from `ess_run`).  `convergence` carries max R-hat, min /
+median ESS and WHICH parameter has the minimum, so a small min-ESS can be traced to
+the coordinate that does not mix.
 
 roofline: dominant kernel = the hierarchical-logit row pass (csrc/rows_kernel.h /
 rows_ga_kernel.h; with NUTS_GA_VARIANT=32 the persistent tree kernel of
@@ -36,7 +46,7 @@ tools/gpu_round.sh (2 x FETCH_SIZE + WRITE_SIZE, the gfx950 correction of
 MI355X_MICROARCH.md), read from profiles/traffic.json together with the hash of the
 kernel sources it was measured on (`traffic_build_matches`).
 
-cpu_baseline (rank 0, N=1 only): the oracle's reference-order leapfrog
+cpu_baseline (`--full`, rank 0, N=1 only): the oracle's reference-order leapfrog
 (`oracle/ref_sampler.Leapfrog` = the restatement that reproduces the reference's
 CpuLeapfrogIntegrator bitwise) over (i) the single-threaded gcc -O3 -march=native
 restatement of logp+grad (stand-in for PyTensor's C linker, which cannot run here),
@@ -98,7 +108,15 @@ def parse():
     ap.add_argument("--ess-draws", type=int, default=1000)
     ap.add_argument("--ess-chains", type=int, default=8, help="chains of the ESS run on each GPU, one after the other (world == 1 only): min-ESS and "
                     "R-hat over several chains instead of a one-chain estimate (0 / 1: the single chain)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true", help="also run what is not the headline: the separate ESS run (--ess-*), the CPU baseline "
+                    "(--cpu-leapfrogs), C3's chains on one GPU (--chains-per-gpu), the oracle's own chains of this shape; a plain run times "
+                    "the K steps and reports them")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="after the timed steps, write what the last timed step returned (its "
+                    "draw and its sampler statistics) as DIR/<name>.npy, float64; ranks other than 0 add _rank<r> to the names")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def kernel_source_hash():
@@ -108,6 +126,27 @@ def kernel_source_hash():
         with open(os.path.join(d, f), "rb") as fh:
             h.update(fh.read())
     return h.hexdigest()[:12]
+
+
+# wall / CPU clocks of the draw and the warning object: not outputs of the computation
+_DUMP_SKIP_STATS = ("perf_counter_diff", "perf_counter_start", "process_time_diff", "warning")
+# NaN placeholders unless the potential estimates its mass matrix's eigenvalues (the diagonal one never does: quadpotential.py)
+_DUMP_IF_ESTIMATED = ("largest_eigval", "smallest_eigval")
+
+
+def dump_outputs(out_dir, rank, draw, stats):
+    """`--dump-outputs DIR`: the last timed step's draw (one position, n float64) and its numeric sampler statistics, one .npy each."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {} if draw is None else {"draw": draw}
+    for k, v in stats.items():
+        if k in _DUMP_SKIP_STATS or not isinstance(v, (bool, int, float, np.bool_, np.number)):
+            continue
+        if k in _DUMP_IF_ESTIMATED and not np.isfinite(v):
+            continue
+        arrays[f"stat_{k}"] = v
+    suffix = f"_rank{rank}" if rank else ""
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}{suffix}.npy"), np.asarray(a, dtype=np.float64))
 
 
 # ---------------------------------------------------------------------------
@@ -375,6 +414,8 @@ def run_rank(args):
         tree = chain.run(K)
         barrier()
         dt = time.perf_counter() - t0
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, rank, None, {"tree_size": tree[-1]})
         leap = float(tree.sum())
         vec = [dt, 0.0, leap, 0.0, 0.0, 0.0, 0.0]        # (no kernel: the roofline block of a stub line reads 0)
         conv, ess_run = None, None
@@ -429,6 +470,8 @@ def run_rank(args):
         dt = time.perf_counter() - t0
         dom_ms, dom_n, _ = step.profile_read()
         step.profile(False)
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, rank, draws[-1], stats_list[-1])
         tree = np.array([s["tree_size"] for s in stats_list])
         n_div = int(sum(bool(s["diverging"]) for s in stats_list))
         leap = float(tree.sum())
@@ -468,7 +511,7 @@ def run_rank(args):
         # does (benchmarks/benchmarks/benchmarks.py:180-198: min ESS / total sampling time).  Reported under "ess_run"; it
         # never enters `value`, `ms_per_step` or the roofline block, which describe exactly the K timed steps above.
         ess_run = None
-        if not ess_ok and args.ess_draws >= ESS_MIN_DRAWS and args.ess_tune >= ESS_MIN_DRAWS:
+        if args.full and not ess_ok and args.ess_draws >= ESS_MIN_DRAWS and args.ess_tune >= ESS_MIN_DRAWS:
             from pymc_amd.sampling import sample_chain
 
             step.sampling_state = initial_state
@@ -578,7 +621,7 @@ def run_rank(args):
         ess_runs = [ess_run]
     if rank == 0:
         out = report(args, world, allv, convs, ess_runs, meta, ess_ok, rccl)
-        if world == 1 and args.cpu_leapfrogs > 0 and not stub:
+        if args.full and world == 1 and args.cpu_leapfrogs > 0 and not stub:
             inv_mass = step._vector("var")
             eps = float(step._scalar("step_size"))
             if c3 or glm:
@@ -589,7 +632,7 @@ def run_rank(args):
                 out["cpu_baseline"] = cpu_baseline_c2(args, spec, draws[-1], eps, inv_mass, args.cpu_leapfrogs,
                                                       (vec[1] / max(leap, 1.0)) if ess_ok else
                                                       (ess_run["min_ess"] / max(ess_run["leapfrogs_total"], 1.0)) if ess_run else None)
-        if c3 and world == 1 and not stub and 2 <= args.chains_per_gpu <= 4:
+        if args.full and c3 and world == 1 and not stub and 2 <= args.chains_per_gpu <= 4:
             try:
                 out["chains_on_one_gpu"] = chains_on_one_gpu(args, spec, local)
             except Exception as e:     # (an extra leg: the line of the timed region is printed whatever happens here)
@@ -756,7 +799,7 @@ def report(args, world, allv, convs, ess_runs, meta, ess_ok, rccl=None):
         "ess_per_sec_is": "the K timed steps" if ess_ok else ("ess_run (separate chain, wall time incl. warmup)" if ess_run else None),
         "ess_per_chain": [float(x) for x in allv[:, 1]] if ess_ok else None,
         "convergence": convs if ess_ok else None,
-        "oracle_convergence": oracle_convergence(args) if ess_ok else None,
+        "oracle_convergence": oracle_convergence(args) if (ess_ok and args.full) else None,
         "ess_run": ess_run,
         "setup": setup,
         "mean_tree_size": leap_total / (K * world),

@@ -86,3 +86,38 @@ def test_under_a_launcher_the_launchers_world_runs():
     assert len(lines) == 1
     out = json.loads(lines[0])
     assert out["n_gpus"] == 2 and out["launch"] == "launched by torch.distributed.run"
+
+
+@pytest.mark.timeout(300)
+def test_dump_outputs_writes_each_ranks_last_timed_step(tmp_path):
+    """`--dump-outputs DIR`: after the K timed steps every rank writes what its last step returned (float64 .npy, ranks other than 0
+    with a `_rank<r>` suffix); a plain run carries none of the `--full` legs."""
+    d = tmp_path / "out"
+    r = subprocess.run([sys.executable, BENCH, "--gpus", "2", "--stub-engine", "--steps", "9", "--warmup", "2", "--dump-outputs", str(d)],
+                       capture_output=True, text=True, env=_env(), timeout=280)
+    assert r.returncode == 0, r.stderr[-2000:]
+    out = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][0])
+    assert out["steps"] == 9 and out["ms_per_step"] > 0
+    assert "cpu_baseline" not in out and out["ess_run"] is None and out["oracle_convergence"] is None
+    assert sorted(os.listdir(d)) == ["stat_tree_size.npy", "stat_tree_size_rank1.npy"]
+    for rk, name in enumerate(["stat_tree_size.npy", "stat_tree_size_rank1.npy"]):
+        a = np.load(d / name)
+        assert a.dtype == np.float64 and a == np.random.default_rng(1000 + rk).choice([15, 31, 63], size=9)[-1]
+
+
+@pytest.mark.timeout(120)
+def test_steps_below_one_is_refused():
+    r = subprocess.run([sys.executable, BENCH, "--stub-engine", "--steps", "0"], capture_output=True, text=True, env=_env(), timeout=100)
+    assert r.returncode == 2 and "--steps" in r.stderr
+
+
+def test_dump_leaves_out_clocks_and_unestimated_eigenvalues(tmp_path):
+    """The eigenvalue statistics are NaN placeholders unless the potential estimates them: dumped only when finite; clocks never."""
+    import bench                      # (the repository root is on sys.path: tests/conftest.py)
+
+    stats = {"energy": -3.5, "tree_size": 7.0, "diverging": False, "largest_eigval": np.nan, "smallest_eigval": np.nan,
+             "perf_counter_diff": 0.1, "warning": None}
+    bench.dump_outputs(str(tmp_path / "a"), 0, np.arange(4.0), stats)
+    assert sorted(os.listdir(tmp_path / "a")) == ["draw.npy", "stat_diverging.npy", "stat_energy.npy", "stat_tree_size.npy"]
+    bench.dump_outputs(str(tmp_path / "b"), 1, None, dict(stats, largest_eigval=2.0, smallest_eigval=0.5))
+    assert "stat_largest_eigval_rank1.npy" in os.listdir(tmp_path / "b") and np.load(tmp_path / "b" / "stat_smallest_eigval_rank1.npy") == 0.5

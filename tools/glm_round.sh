@@ -10,7 +10,7 @@ export TMPDIR=/tmp
 cd $R
 HASH=$(python -c "import bench; print(bench.kernel_source_hash())")
 if [[ $STAGES == *b* ]]; then
-  timeout 900 python bench.py --workload glm --steps 200 --warmup 300 --ess-tune 0 > $OUT/bench_glm_$TAG.json 2> $OUT/bench_glm_$TAG.err; echo "bench rc=$?" >> $OUT/bench_glm_$TAG.err
+  timeout 900 python bench.py --workload glm --steps 200 --warmup 300 --ess-tune 0 --full > $OUT/bench_glm_$TAG.json 2> $OUT/bench_glm_$TAG.err; echo "bench rc=$?" >> $OUT/bench_glm_$TAG.err
   head -c 1800 $OUT/bench_glm_$TAG.json; echo
 fi
 if [[ $STAGES == *s* ]]; then
