@@ -110,13 +110,9 @@ struct nuts_model {
   bool has_prog = false;   // some factor carries an expression program or a gathered operand: kernels with the interpreter compiled in
   int rows_rpl = 2, rows_alternate = 1, rows_flip = 0, rows_occ = 4;
   int vector_one_xcd = 0;
-  int ga_variant = 42;         // 10 x (waves per SIMD of the register budget) + tiles in flight per wave
   int ga_struct_ok = 0;        // the spec is exactly what the group-aligned row pass evaluates in closed form (compile_spec)
   int ga_par = 0;              // parity of the last group-aligned launch (its block partials / local parts are double-buffered)
-  unsigned* ga_sync = nullptr; // progress words of the persistent tree kernel (rows_ga_tree.h)
-  int ga_tree_ok = 0;          // the whole grid of k_tree_ga is resident at once on this device (checked at model creation)
-  long long* tree_dbg = nullptr; int tree_dbg_leaf = 0;   // NUTS_GA_TREE_DBG=<leaf + 1>: per-workgroup timeline of one leaf
-  int64_t dom_units = 0;       // leapfrog passes covered by the timed launches (a tree launch covers a whole tree)
+  int64_t dom_units = 0;       // leapfrog passes covered by the timed launches
   int explicit_pre = 0;        // the position must be materialised before the dense pass (MvNormal node)
   int64_t alg_bytes = 0;
   // profiling of the dominant kernel
@@ -203,9 +199,6 @@ struct nuts_group {
   GalConst* gal_konst_dev = nullptr;           // [GAL_MAXC]
   GalConst gal_konst_host[GAL_MAXC] = {};      // ... as last uploaded
   bool gal_konst_set[GAL_MAXC] = {};
-  int gbm_occ = 2;                             // option NUTS_GBM_OCC (A/B): register budget of the group-block pass's merged launch
-  int gal_pf3 = 0;                             // option NUTS_GAL_PF3 (A/B): tiles requested three ahead instead of two (four and eight chains)
-  int gal_occ5 = 1;                            // option NUTS_GAL_OCC5 (A/B, default 1): four to six chains at the 96-register budget (five waves per SIMD: every group of the benchmark resident) instead of 128
   int rows_lds = 1;                            // option NUTS_ROWS_GROUP_LDS (read when the first member joins); 0: the round-5 kernel (<= 4 chains)
 };
 static_assert(GAM_MAXNC == MVM_MAXC && GAL_MAXC == GAM_MAXC && GAL_MAXC <= GRP_MAXC, "group sizes");
@@ -319,15 +312,10 @@ static void group_flush_rows_locked(nuts_group* g) {
     for (int c = nc; c < GAL_MAXC; ++c) { ma.c[c] = ma.c[0]; ma.k[c] = ma.k[0]; }
     ma.nc = nc; ma.rev = rev;
     const dim3 grid(nc * (md.lg.ga_nblk + 1)), block(WAVE * GB_W);
-    // (register budget by the rounds the grid needs: NUTS_GBM_OCC = 2 / 4 / 6 waves per SIMD, i.e. 1 / 2 / 3 workgroups per CU)
-#define GBM_LAUNCH(DXX)                                                                                              \
-    switch (g->gbm_occ) {                                                                                            \
-      default: hipLaunchKernelGGL((k_rows_gb_multi<8, DXX, 2>), grid, block, 0, g->stream, md, ma); break;           \
-      case 6: hipLaunchKernelGGL((k_rows_gb_multi<8, DXX, 6>), grid, block, 0, g->stream, md, ma); break;            \
-      case 4: hipLaunchKernelGGL((k_rows_gb_multi<8, DXX, 4>), grid, block, 0, g->stream, md, ma); break;            \
-    }
-    if (md.lg.ga_dx == 7) GBM_LAUNCH(7) else GBM_LAUNCH(8)
-#undef GBM_LAUNCH
+    // (register budget of two waves per SIMD, one workgroup per CU.  Measured at C2-S with 4 / 8 chains: 107 k / 128 k at these
+    // unbounded 175 registers, 88 k / 114 k at 128, 58 k / 66 k at 80 -- the spills cost more than the rounds they save)
+    if (md.lg.ga_dx == 7) hipLaunchKernelGGL((k_rows_gb_multi<8, 7, 2>), grid, block, 0, g->stream, md, ma);
+    else hipLaunchKernelGGL((k_rows_gb_multi<8, 8, 2>), grid, block, 0, g->stream, md, ma);
     g->launches[nc]++;
     g->npend = 0;
     g->gen.fetch_add(1, std::memory_order_release);
@@ -339,7 +327,8 @@ static void group_flush_rows_locked(nuts_group* g) {
   // kernel for every launch of two chains or more (tests, A/B).
   if (g->rows_lds && (nc > GAM_MAXNC || (nc >= 2 && g->rows_lds == 2))) {
     // one wave per chain, the tiles shared through LDS (rows_gal_kernel.h).  OCC: waves per SIMD the register budget is sized for:
-    // four (128 registers: the two rows of a lane side by side without a spill in the stream).
+    // four (128 registers: the two rows of a lane side by side without a spill in the stream); five (96 registers) at four to six
+    // chains, where every group of the benchmark is then resident at once (128 registers measured 32.6 k against 34.7 k there).
     const dim3 grid(GAL_MAXC + md.lg.G);
 #define GAL_LAUNCH(NC, DXX, OCC)                                                                                     \
   {                                                                                                                  \
@@ -348,28 +337,20 @@ static void group_flush_rows_locked(nuts_group* g) {
     la.rev = rev; la.pad = 0;                                                                                        \
     hipLaunchKernelGGL((k_rows_gal<NC, DXX, OCC>), grid, dim3(WAVE * NC), 0, g->stream, md, (const GalConst*)g->gal_konst_dev, la); \
   }
-#define GAL_LAUNCH3(NC, DXX, OCC)   /* three tiles requested ahead (A/B: NUTS_GAL_PF3) */                             \
-  {                                                                                                                  \
-    GalArgs<NC> la;                                                                                                  \
-    for (int c = 0; c < NC; ++c) gal_leaf(la.c[c], g->gpend[order[c]]);                                              \
-    la.rev = rev; la.pad = 0;                                                                                        \
-    hipLaunchKernelGGL((k_rows_gal<NC, DXX, OCC, 3>), grid, dim3(WAVE * NC), 0, g->stream, md, (const GalConst*)g->gal_konst_dev, la); \
-  }
 #define GAL_BY_NC(DXX)                                                                                               \
   switch (nc) {                                                                                                      \
     case 2: GAL_LAUNCH(2, DXX, 4) break;                                                                             \
     case 3: GAL_LAUNCH(3, DXX, 4) break;                                                                             \
-    case 4: if (g->gal_occ5) GAL_LAUNCH(4, DXX, 5) else if (g->gal_pf3) GAL_LAUNCH3(4, DXX, 4) else GAL_LAUNCH(4, DXX, 4) break; \
-    case 5: if (g->gal_occ5) GAL_LAUNCH(5, DXX, 5) else GAL_LAUNCH(5, DXX, 4) break;                                 \
-    case 6: if (g->gal_occ5) GAL_LAUNCH(6, DXX, 5) else GAL_LAUNCH(6, DXX, 4) break;                                 \
+    case 4: GAL_LAUNCH(4, DXX, 5) break;                                                                             \
+    case 5: GAL_LAUNCH(5, DXX, 5) break;                                                                             \
+    case 6: GAL_LAUNCH(6, DXX, 5) break;                                                                             \
     case 7: GAL_LAUNCH(7, DXX, 4) break;                                                                             \
-    default: if (g->gal_pf3) GAL_LAUNCH3(8, DXX, 4) else GAL_LAUNCH(8, DXX, 4) break;                                \
+    default: GAL_LAUNCH(8, DXX, 4) break;                                                                            \
   }
     gal_upload_consts();
     if (md.lg.ga_dx == 7) GAL_BY_NC(7) else GAL_BY_NC(8)
 #undef GAL_BY_NC
 #undef GAL_LAUNCH
-#undef GAL_LAUNCH3
     g->launches[nc]++;
     g->npend = 0;
     g->gen.fetch_add(1, std::memory_order_release);
@@ -625,30 +606,17 @@ static void launch_dense(nuts_model* m, const ArenaDev& A, const EvalIO& io, int
         default: hipLaunchKernelGGL((k_rows_gb<7>), grid, block, 0, m->stream, ga); break;
       }
     } else {
-#define GA_LAUNCH(DD, OO, PP) hipLaunchKernelGGL((k_rows_ga<DD, 2, OO, PP>), grid, block, 0, m->stream, ga)
-#define GA_BY_D(OO, PP)                      \
-    switch (md.lg.D) {                       \
-      case 8: if (md.lg.ga_dx == 7) hipLaunchKernelGGL((k_rows_ga<8, 2, OO, PP, 7>), grid, block, 0, m->stream, ga); \
-              else GA_LAUNCH(8, OO, PP); break;   \
-      case 4: GA_LAUNCH(4, OO, PP); break;   \
-      default: GA_LAUNCH(2, OO, PP); break;  \
-    }
-    if (md.lg.D != 8 && md.lg.D != 4 && md.lg.D != 2) {   // the other covariate counts: the default budget only
       switch (md.lg.D) {
-        case 1: GA_LAUNCH(1, 4, 2); break;
-        case 3: GA_LAUNCH(3, 4, 2); break;
-        case 5: GA_LAUNCH(5, 4, 2); break;
-        case 6: GA_LAUNCH(6, 4, 2); break;
-        default: GA_LAUNCH(7, 4, 2); break;
+        case 8: if (md.lg.ga_dx == 7) hipLaunchKernelGGL((k_rows_ga<8, 2, 7>), grid, block, 0, m->stream, ga);
+                else hipLaunchKernelGGL((k_rows_ga<8, 2>), grid, block, 0, m->stream, ga); break;
+        case 4: hipLaunchKernelGGL((k_rows_ga<4, 2>), grid, block, 0, m->stream, ga); break;
+        case 2: hipLaunchKernelGGL((k_rows_ga<2, 2>), grid, block, 0, m->stream, ga); break;
+        case 1: hipLaunchKernelGGL((k_rows_ga<1, 2>), grid, block, 0, m->stream, ga); break;
+        case 3: hipLaunchKernelGGL((k_rows_ga<3, 2>), grid, block, 0, m->stream, ga); break;
+        case 5: hipLaunchKernelGGL((k_rows_ga<5, 2>), grid, block, 0, m->stream, ga); break;
+        case 6: hipLaunchKernelGGL((k_rows_ga<6, 2>), grid, block, 0, m->stream, ga); break;
+        default: hipLaunchKernelGGL((k_rows_ga<7, 2>), grid, block, 0, m->stream, ga); break;
       }
-    } else
-    switch (m->ga_variant) {   // (register budget, tiles in flight): see rows_ga_kernel.h
-      case 32: GA_BY_D(3, 2) break;
-      case 33: GA_BY_D(3, 3) break;
-      default: GA_BY_D(4, 2) break;
-    }
-#undef GA_BY_D
-#undef GA_LAUNCH
     }
   } else if (md.has_logit) {
     const int rev = m->rows_alternate ? (m->rows_flip ^= 1) : 0;
@@ -1488,16 +1456,10 @@ extern "C" nuts_model* nuts_model_create(const nuts_model_spec* s) {
         tile0[g + 1] = tile0[g] + (int32_t)T;
       }
       const int64_t n_tiles = tile0[lg.G];
-      m->ga_variant = env_int("NUTS_GA_VARIANT", 42);
-      if (m->ga_variant != 32 && m->ga_variant != 33) m->ga_variant = 42;
-      const int occ = m->ga_variant / 10;
-      int W = std::min(GA_MAXW, (4 * occ * cus) / std::max(lg.G, 1));   // all G workgroups resident at once (4 occ waves per CU)
+      int W = std::min(GA_MAXW, (16 * cus) / std::max(lg.G, 1));   // all G workgroups resident at once (4 waves per SIMD, 16 per CU)
       if (env_int("NUTS_ROWS_GA_W", 0) > 0) W = std::max(1, std::min(GA_MAXW, env_int("NUTS_ROWS_GA_W", 0)));
       const double meanT = (double)n_tiles / std::max(lg.G, 1);
       bool use = false;
-      // (every covariate count 1 .. 8 has an instantiation of the group-aligned pass; the register-budget variants 32 / 33 exist
-      // for D = 2, 4, 8 only)
-      if (!d_pow2) m->ga_variant = 42;
       if (want >= 2) { use = m->ga_struct_ok && m->ept == 1; W = std::max(1, W); }
       else if (want == 1) use = m->ga_struct_ok && m->ept == 1 && W >= 1 && lg.G >= 2 * cus && meanT >= 4.0 * W && (double)maxT <= 1.5 * meanT + 1.0;
       // group-BLOCK pass (rows_gb_kernel.h) for small groups: the same closed-form model, a workgroup owns GPW whole groups and
@@ -1588,28 +1550,7 @@ extern "C" nuts_model* nuts_model_create(const nuts_model_spec* s) {
         if (lg.ga_part) hipMemset(lg.ga_part, 0, (size_t)lg.G * PART_STRIDE * sizeof(double));
         if (lg.ga_bpart) hipMemset(lg.ga_bpart, 0, bpart_len * sizeof(double));
         if (lg.ga_ticket) hipMemset(lg.ga_ticket, 0, lg.ga_nblk * sizeof(unsigned));
-        if (env_int("NUTS_GA_TREE_DBG", 0) > 0) {
-          m->tree_dbg_leaf = env_int("NUTS_GA_TREE_DBG", 0) - 1;
-          m->tree_dbg = m->keep(dev_alloc<long long>((size_t)lg.G * 8));
-          if (m->tree_dbg) hipMemset(m->tree_dbg, 0, (size_t)lg.G * 8 * sizeof(long long));
-        }
-        m->ga_sync = m->keep(dev_alloc<unsigned>(GA_SYNC_WORDS));
-        if (m->ga_sync) hipMemset(m->ga_sync, 0, GA_SYNC_WORDS * sizeof(unsigned));
         m->rows_grid = gpw ? lg.ga_nblk : lg.G;
-        // persistent tree kernel (rows_ga_tree.h): needs every one of its G + 1 workgroups resident at once.  The occupancy
-        // query is asked for the real block size and capped by the wave slots of the register budget; the query can be
-        // optimistic (MI355X guide, "Residency and cooperative launch"), which is why every wait in the kernel is bounded.
-        m->ga_tree_ok = 0;
-        // (only at the 168-register budget, variant 32: at 128 registers the allocator spills inside the streaming loop)
-        if (D == 8 && m->ga_variant == 32 && !gpw && lg.ga_naux == 0 && env_int("NUTS_GA_TREE", 1) != 0) {
-          int per_cu = 0;
-          const hipError_t e = lg.ga_dx == 7 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_tree_ga<3, 7>, WAVE * W, 0)
-                                             : hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_tree_ga<3, 8>, WAVE * W, 0);
-          if (e == hipSuccess) {
-            const int hw = std::min(per_cu, (4 * occ) / std::max(W, 1));   // `occ` waves per SIMD at this register budget
-            m->ga_tree_ok = (int64_t)hw * cus >= (int64_t)lg.G + 1;
-          }
-        }
       }
     }
     if (!lg.ga) {
@@ -1971,14 +1912,6 @@ extern "C" int nuts_model_debug_ticks(nuts_model* m, int64_t* out) {
   return NUTS_OK;
 }
 
-extern "C" int nuts_model_debug_tree(nuts_model* m, int64_t* out, int64_t cap) {
-  if (!m || !out) return NUTS_E_ARG;
-  if (!m->tree_dbg) { g_err = "no per-workgroup timeline (create the model with NUTS_GA_TREE_DBG=<leaf + 1>)"; return NUTS_E_ARG; }
-  HIPCHK(hipStreamSynchronize(m->stream));
-  const int64_t nwords = std::min<int64_t>(cap, (int64_t)m->md.lg.G * 8);
-  HIPCHK(hipMemcpy(out, m->tree_dbg, (size_t)nwords * sizeof(long long), hipMemcpyDeviceToHost));
-  return NUTS_OK;
-}
 extern "C" int32_t nuts_model_ndim(const nuts_model* m) { return m ? m->md.n : -1; }
 extern "C" int nuts_model_get_scalar(const nuts_model* m, const char* name, double* out) {
   if (!m || !name || !out) return NUTS_E_ARG;
@@ -1993,12 +1926,10 @@ extern "C" int nuts_model_get_scalar(const nuts_model* m, const char* name, doub
   else if (k == "mvn_row_aligned") *out = m->md.has_mvn ? m->md.mv.aligned : 0;
   else if (k == "rows_waves") *out = m->md.lg.ga ? m->md.lg.ga_w : m->md.lg.n_waves;
   else if (k == "lean") *out = m->md.lean_ok;
-  else if (k == "tree_kernel_ok") *out = m->ga_tree_ok;
-  else if (k == "rows_stored_columns") *out = m->md.lg.ga ? m->md.lg.ga_dx : m->md.lg.D;
   else if (k == "chain_group_kind") {   // what a chain group of this model's chains would merge: 0 nothing, 1 the MvNormal row-aligned pass, 2 the group-aligned row pass
     const RowsDev& lg = m->md.lg;
     const bool is_mvn = m->md.has_mvn && (m->md.mv.aligned == 4 || m->md.mv.aligned == 8 || m->md.mv.aligned == 16);
-    const bool is_rows = m->md.has_logit && !m->md.has_mvn && lg.ga && lg.ga_naux == 0 && lg.D == 8 && m->ga_struct_ok == 1 && (lg.ga_gpw > 0 || m->ga_variant == 42);
+    const bool is_rows = m->md.has_logit && !m->md.has_mvn && lg.ga && lg.ga_naux == 0 && lg.D == 8 && m->ga_struct_ok == 1;
     *out = is_mvn ? 1.0 : (is_rows ? (lg.ga_gpw > 0 ? 3.0 : 2.0) : 0.0);   // (3: the group-block row pass, round 6)
   }
   // 1: chains of this model can form a WIDE group (up to 16 chains per launch through the matrix cores, mvn_mfma_kernel.h) once the
@@ -2206,17 +2137,12 @@ struct nuts_chain {
   double* kin_part = nullptr;    // [nblk] kinetic-energy partials of the initial state
   int64_t cache_epoch = -1;      // model data epoch the start-state cache belongs to
   int fold_ctl = 1;              // lean path: overlap the control work of leaf j with the row pass of leaf j+1
-  int tree_mode = 0;             // group-aligned row pass: one persistent launch per NUTS tree (rows_ga_tree.h)
-  int64_t tree_launches = 0;
   CtlJob pend{}; bool pend_valid = false;   // control work of a doubling's last leaf waiting for the next doubling's first row pass
   bool defer_last_ctl = false; int xfold = 1;   // NUTS_XFOLD: fold control work across doublings (group-aligned row pass)
   // row-aligned MvNormal pass: the doubling being queued will be followed (look-ahead) by one in direction `next_dir`; its last
   // leaf then also materialises the first half of that doubling's first leaf (EvalIO.pre_next 1 / 3), and `pre_done` tells the
   // first leaf of the next doubling that its k_leaf_pre launch is not needed
   int next_dir = 0; bool pre_done = false; int xpre = 1;
-  int tree_opts = 0;             // GA_TREE_* switches (NUTS_GA_TREE_OPTS, NUTS_GA_TREE_TICKS)
-  int tree_prof_pair = 0;        // ... which event pair that is
-  int tree_prof_pending = 0;     // the last tree launch is being timed: its leaf count is added when the draw's record arrives
   int spec_max = 10, last_depth = 0;   // look-ahead over the doublings, as deep as the previous tree went (run_tree)
   int pipe_draws = 1;                  // NUTS_PIPE_DRAWS, latched at creation: post-tuning draws of a batch are queued behind each other
   int logs_done = 0, logs_total = 0;  // logarithms of the pre-drawn uniforms taken / needed at most this draw
@@ -2394,10 +2320,6 @@ extern "C" nuts_chain* nuts_chain_create(nuts_model* m, const nuts_chain_config*
   c->wb_mean = c->keep(dev_alloc<double>(n)); c->wb_m2 = c->keep(dev_alloc<double>(n));
   A.var = c->var; A.inv_stds = c->inv_stds;
   A.ga_ticket = m->md.lg.ga ? m->md.lg.ga_ticket : nullptr; A.ga_nticket = m->md.lg.ga ? m->md.lg.ga_nblk : 0;
-  A.ga_sync = m->md.lg.ga ? m->ga_sync : nullptr;
-  // NUTS_GA_TREE=0: one launch per leapfrog (also what several chains SHARING a GPU must use: the tree kernel needs the chip)
-  c->tree_opts = env_int("NUTS_GA_TREE_OPTS", 0) | (env_int("NUTS_GA_TREE_TICKS", 0) << GA_TREE_TICK_SHIFT);
-  c->tree_mode = m->md.lg.ga && m->ga_tree_ok && !c->dense && m->md.lean_ok && env_int("NUTS_GA_TREE", 1) != 0;
   if (c->full_adapt) {
     const size_t nn = (size_t)n * n;
     c->fa_initial_cov.assign(cfg->dense_cov, cfg->dense_cov + nn);
@@ -2508,7 +2430,7 @@ extern "C" int nuts_group_add(nuts_group* g, nuts_chain* c) {
   const bool is_mvn = m->md.has_mvn && (mv.aligned == 4 || mv.aligned == 8);
   // the hierarchical-logit rows on the group-aligned pass, closed-form model (the benchmark's), D = 8: rows_ga_multi_kernel.h
   // ... or on the group-BLOCK pass (small groups, C2-S): rows_gb_multi_kernel.h
-  const bool is_rows = m->md.has_logit && !m->md.has_mvn && lg.ga && lg.ga_naux == 0 && lg.D == 8 && m->ga_struct_ok == 1 && (lg.ga_gpw > 0 || m->ga_variant == 42);
+  const bool is_rows = m->md.has_logit && !m->md.has_mvn && lg.ga && lg.ga_naux == 0 && lg.D == 8 && m->ga_struct_ok == 1;
   const int rows_kind = lg.ga_gpw > 0 ? 3 : 2;
   if (!(is_mvn || is_rows) || c->dense || c->host_pot) {
     g_err = "nuts_group_add: chain groups advance models that are one constant-covariance MvNormal node on the row-aligned pass or the "
@@ -2579,9 +2501,6 @@ extern "C" int nuts_group_add(nuts_group* g, nuts_chain* c) {
   std::lock_guard<std::mutex> lk(g->mu);
   g->cap = cap;
   g->rows_lds = rows_lds;
-  // (NUTS_GBM_OCC, measured at C2-S with 4 / 8 chains: 107 k / 128 k at the unbounded 175 registers, 88 k / 114 k at 128, 58 k / 66 k
-  // at 80 -- the spills cost more than the rounds they save)
-  if (g->n == 0) { g->gal_occ5 = env_int("NUTS_GAL_OCC5", 1); g->gal_pf3 = env_int("NUTS_GAL_PF3", 0); g->gbm_occ = env_int("NUTS_GBM_OCC", 2); }
   for (int i = 0; i < cap; ++i)
     if (!g->member[i]) { g->member[i] = m; m->gslot = i; break; }
   g->n++;
@@ -2950,49 +2869,6 @@ static inline void enqueue_leaf(nuts_chain* c, const Geometry& gm, int j, int d,
   c->leapfrogs++;
 }
 
-// The same transition as ONE launch of the persistent tree kernel (rows_ga_tree.h): the leaf loop and the doubling loop run on
-// the device, the host waits for the status word of the whole tree.  Every logarithm the tree can consume must be on the
-// device before the launch (`ensure_logs` up to the worst case).
-static int run_tree_ga(nuts_chain* c, const double* uniforms, double step_size, int max_depth, unsigned* flags_out, bool* exhausted_out,
-                       int* cursor_out = nullptr) {
-  nuts_model* m = c->m;
-  ArenaDev& A = c->A;
-  int rc = ensure_logs(c, (1 << max_depth) + max_depth + 1);
-  if (rc) return rc;
-  const int seq = ++c->seq;
-  GaTreeArgs ga{};
-  ga.md = m->md; ga.A = A;
-  ga.max_depth = max_depth;
-  ga.spec_depth = c->last_depth - 1;   // speculate across doubling boundaries as deep as the previous draw's tree went
-  ga.rev0 = m->rows_flip; ga.par0 = m->ga_par; ga.alternate = m->rows_alternate;
-  ga.first_dir = uniforms[0] < 0.5 ? 1 : -1;
-  ga.seq = seq;
-  ga.Emax = c->cfg.Emax; ga.eps_abs = step_size;
-  ga.st = c->st_dev;
-  ga.timeout = (long long)env_int("NUTS_GA_TREE_TIMEOUT_MS", 50) * 100000ll;   // 100 MHz ticks
-  ga.opts = c->tree_opts;
-  ga.dbg = m->tree_dbg; ga.dbg_leaf = m->tree_dbg_leaf;
-  const bool prof = m->profile && m->ev_used + 2 <= m->ev.size();
-  if (prof) hipEventRecord(m->ev[m->ev_used], m->stream);
-  if (m->md.lg.ga_dx == 7) hipLaunchKernelGGL((k_tree_ga<3, 7>), dim3(m->rows_grid + 1), dim3(WAVE * m->md.lg.ga_w), 0, m->stream, ga);
-  else hipLaunchKernelGGL((k_tree_ga<3, 8>), dim3(m->rows_grid + 1), dim3(WAVE * m->md.lg.ga_w), 0, m->stream, ga);
-  if (prof) { hipEventRecord(m->ev[m->ev_used + 1], m->stream); c->tree_prof_pair = (int)(m->ev_used / 2); m->ev_used += 2; c->tree_prof_pending = 1; }
-  m->dom_launches++;
-  c->tree_launches++;
-  unsigned flags = 0;
-  rc = wait_status(c, seq, &flags, cursor_out);
-  if (rc) return rc;
-  if (flags & ST_TIMEOUT) {
-    g_err = "persistent tree kernel: a wait between workgroups timed out (are all of its workgroups resident? another process on "
-            "this GPU? run with NUTS_GA_TREE=0)";
-    hipStreamSynchronize(m->stream);
-    return NUTS_E_HIP;
-  }
-  *flags_out = flags;
-  *exhausted_out = !(flags & (ST_DIVERGING | ST_TURNING));
-  return NUTS_OK;
-}
-
 // The doubling loop of one transition (NUTS._hamiltonian_step, nuts.py:204-225): queue the leaves of each doubling, wait for the
 // status word of its last leaf.  `uniforms`: the host copy of the pre-drawn `step.rng.random()` values of THIS draw.
 static int run_tree(nuts_chain* c, const double* uniforms, double step_size, int max_depth, unsigned* flags_out, bool* exhausted_out,
@@ -3100,11 +2976,6 @@ static int finish_draw_host(nuts_chain* c, const DrawOut& o, bool adapt, bool ex
   const int n = c->n;
   ArenaDev& A = c->A;
   const double accept = std::exp(o.log_accept_sum) / o.n_proposals;
-  if (c->tree_mode) {
-    c->last_depth = o.depth;
-    c->leapfrogs += o.n_proposals;
-    if (c->tree_prof_pending) { c->m->dom_units += o.n_proposals; c->m->ev_units[c->tree_prof_pair] = std::max(1, (int)o.n_proposals); c->tree_prof_pending = 0; }
-  }
   c->da.update(accept, adapt);
   int rc = potential_update(c, result_dev, result_dev + c->n);
   if (rc) return rc;
@@ -3197,8 +3068,7 @@ extern "C" int nuts_chain_draw(nuts_chain* c, const double* q0, const double* no
   const auto tb = clk::now();
   c->t_begin += std::chrono::duration<double>(tb - t0).count();
   unsigned flags = 0;
-  rc = c->tree_mode ? run_tree_ga(c, uniforms, step_size, max_depth, &flags, &exhausted)
-                    : run_tree(c, uniforms, step_size, max_depth, &flags, &exhausted);
+  rc = run_tree(c, uniforms, step_size, max_depth, &flags, &exhausted);
   if (rc) return rc;
   const auto tl = clk::now();
   c->t_loop += std::chrono::duration<double>(tl - tb).count();
@@ -3295,7 +3165,7 @@ static int draw_many_general(nuts_chain* c, const double* q0, const double* norm
   // kernel, and this draw's record -- statistics only -- is read while the next tree is already running.  One host round trip per draw
   // (the status) instead of three (status, record, then an idle queue to restart): ~50 us of GPU idle per draw on C2-S / C3
   // (profiles/r03g_profile_c3.txt: 50.7 us idle before k_draw_start).  A divergent draw is finished synchronously, as before.
-  const bool pipe = !c->tune && !c->tree_mode && !c->full_adapt && c->pipe_draws;   // (the option is latched when the chain is created)
+  const bool pipe = !c->tune && !c->full_adapt && c->pipe_draws;   // (the option is latched when the chain is created)
   struct Pending {
     bool valid = false; int k = 0; unsigned seq = 0; bool exhausted = false, adapt = false; size_t consumed_after = 0; int cursor = 0;
     double perf_start = 0.0, wall = 0.0, cpu = 0.0;
@@ -3364,8 +3234,7 @@ static int draw_many_general(nuts_chain* c, const double* q0, const double* norm
     int cursor = 0;
     const auto ta = clk::now();
     c->tm_start += secs(t0, ta);
-    rc = c->tree_mode ? run_tree_ga(c, h_u + consumed, step_size, max_depth, &flags, &exhausted, &cursor)
-                      : run_tree(c, h_u + consumed, step_size, max_depth, &flags, &exhausted, &cursor);
+    rc = run_tree(c, h_u + consumed, step_size, max_depth, &flags, &exhausted, &cursor);
     const auto tb = clk::now();
     c->tm_tree += secs(ta, tb);
     if (rc) break;
@@ -3724,11 +3593,10 @@ extern "C" int nuts_chain_get_scalar(nuts_chain* c, const char* name, double* ou
   else if (k == "bg_count") *out = c->bg_count;
   else if (k == "step_size") *out = c->step_size;
   else if (k == "leapfrogs") *out = (double)c->leapfrogs;
-  else if (k == "tree_kernel") *out = (double)c->tree_mode;
+  else if (k == "tree_kernel" || k == "tree_launches") *out = 0.0;   // (the persistent tree kernel is gone; bench.py and older tests still ask)
   else if (k == "fa_fg_n") *out = c->fa_fg_n;
   else if (k == "fa_bg_n") *out = c->fa_bg_n;
   else if (k == "fa_previous_update") *out = (double)c->fa_previous_update;
-  else if (k == "tree_launches") *out = (double)c->tree_launches;
   else if (k == "single_launch") *out = c->small ? 1.0 : 0.0;
   else if (k == "window_switched") *out = c->window_switched ? 1.0 : 0.0;
   else if (k == "t_begin") *out = c->t_begin;

@@ -79,14 +79,10 @@ struct ArenaDev {
                                // nullptr (single-launch path): the control code takes log(u) itself
   unsigned* ga_ticket;         // arrival counters of the group-aligned row pass (rows_ga_kernel.h), reset at the end of a draw
   int ga_nticket;
-  unsigned* ga_sync;           // [GA_SYNC_WORDS] progress words of the persistent tree kernel (rows_ga_tree.h), reset at the start of a draw
+  void* reserved;              // unused: holds the kernels' argument layout (without it every field behind moved, and C2-S ran 1 % slower)
   const double* kin_user;      // NUTS_POT_HOST: the kinetic energy the host's `energy` / `velocity_energy` returned for the state the
                                // next control kernel looks at (nullptr: kinetic = p.v / 2, the dots the kernels took)
 };
-#define GA_SYNC_DONE 0         // number of block partials published since the start of the draw: leaf L is complete at (L + 1) ga_nblk
-#define GA_SYNC_CTL 1          // leaves whose control work is finished (and written back)
-#define GA_SYNC_ERR 2          // != 0: a wait inside the tree kernel timed out (1: row workgroup, 2: control workgroup)
-#define GA_SYNC_WORDS 4
 
 // Lives in pinned, device-mapped host memory.  `word[seq % ST_SLOTS]` = (sequence number << 32) | ST_* flags is written with ONE
 // system-scope store by the control work of the LAST leaf of a doubling; the host spins on it instead of paying a stream
@@ -98,7 +94,6 @@ struct ArenaDev {
 #define ST_DIVERGING 4u
 #define ST_BAD_ENERGY 8u
 #define ST_DIR_POS 16u
-#define ST_TIMEOUT 32u   // persistent tree kernel: a wait on another workgroup did not complete (not all workgroups resident?)
 #define ST_SLOTS 4   // doublings publish round-robin (the host may have queued the next doubling before reading this one)
 struct HostStatus {
   unsigned long long word[ST_SLOTS];
@@ -1258,7 +1253,6 @@ __device__ __forceinline__ double slot_sum_finish(const double (&v)[SLOT_SUM_MAX
   return wave_sum(acc);
 }
 
-// AGENT: the records were written by other workgroups of THIS launch (persistent tree kernel, rows_ga_tree.h).
 // `nt` (optional): the number of threads of the workgroup that take part (the others have left), if not all of them.
 // BATCH: partial records in flight per thread while they are summed (sum_strided): 8 covers the paths with a few dozen records;
 // the group-block pass (rows_gb_kernel.h) has hundreds and asks for more -- a template parameter so that the register needs of
@@ -1275,7 +1269,7 @@ struct CtlLds {
   Ctl s_ctl;
 };
 
-template <bool AGENT = false, int BATCH = 8, bool PF = false>
+template <int BATCH = 8, bool PF = false>
 __device__ __forceinline__ void control_lean_in(const ModelDev& md, const ArenaDev& A, const EvalIO& io, int j, int d, double Emax,
                                                 int max_depth, HostStatus* st, int seq, const LeanSrc src, int nt, bool have_upf,
                                                 UniPrefetch upf, CtlLds& lds) {
@@ -1308,14 +1302,8 @@ __device__ __forceinline__ void control_lean_in(const ModelDev& md, const ArenaD
   if (mine) {
     def_i = md.deferred_g[2 * tid]; def_k = md.deferred_g[2 * tid + 1];
     if (PF && tree) merge_prefetch(A, lf, j, def_i, mpf);
-    if (AGENT) {
-      const double* dl = src.def_loc + 4 * tid;
-      l01 = make_double2(ld_agent(dl), ld_agent(dl + 1));
-      l23 = make_double2(ld_agent(dl + 2), ld_agent(dl + 3));
-    } else {
-      l01 = reinterpret_cast<const double2*>(src.def_loc)[2 * tid];
-      l23 = reinterpret_cast<const double2*>(src.def_loc)[2 * tid + 1];
-    }
+    l01 = reinterpret_cast<const double2*>(src.def_loc)[2 * tid];
+    l23 = reinterpret_cast<const double2*>(src.def_loc)[2 * tid + 1];
   }
   // ---- fixed-order sums of the per-workgroup partials this leaf needs: (slot, chunk) pairs in parallel ----
   const int nlg = md.has_logit ? lg.D : 0;
@@ -1350,7 +1338,7 @@ __device__ __forceinline__ void control_lean_in(const ModelDev& md, const ArenaD
     for (int t = tid; t < nn * CTL_CHUNKS; t += NT) {
       const int c = t % CTL_CHUNKS, k = need_slot(t / CTL_CHUNKS);
       const int b0 = c * per, b1 = min(src.nblk, (c + 1) * per);
-      s_chunk[c][k] = sum_strided<AGENT, BATCH>(src.part + k, src.stride, b0, b1);
+      s_chunk[c][k] = sum_strided<BATCH>(src.part + k, src.stride, b0, b1);
     }
   }
   __syncthreads();
@@ -1420,20 +1408,20 @@ __device__ __forceinline__ void control_lean_in(const ModelDev& md, const ArenaD
   TICK(md, ctk, 13);
 }
 
-template <bool AGENT = false, int BATCH = 8, bool PF = false>
+template <int BATCH = 8, bool PF = false>
 __device__ __forceinline__ void control_lean(const ModelDev& md, const ArenaDev& A, const EvalIO& io, int j, int d, double Emax,
                                              int max_depth, HostStatus* st, int seq, const LeanSrc src, int nt, bool have_upf,
                                              UniPrefetch upf) {
   __shared__ CtlLds lds;
-  control_lean_in<AGENT, BATCH, PF>(md, A, io, j, d, Emax, max_depth, st, seq, src, nt, have_upf, upf, lds);
+  control_lean_in<BATCH, PF>(md, A, io, j, d, Emax, max_depth, st, seq, src, nt, have_upf, upf, lds);
 }
 
-template <bool AGENT = false, int BATCH = 8, bool PF = false>
+template <int BATCH = 8, bool PF = false>
 __device__ __forceinline__ void control_lean(const ModelDev& md, const ArenaDev& A, const EvalIO& io, int j, int d, double Emax,
                                              int max_depth, HostStatus* st, int seq, const LeanSrc src, int nt = 0) {
   UniPrefetch upf;
   uni_prefetch_none(upf);
-  control_lean<AGENT, BATCH, PF>(md, A, io, j, d, Emax, max_depth, st, seq, src, nt, false, upf);
+  control_lean<BATCH, PF>(md, A, io, j, d, Emax, max_depth, st, seq, src, nt, false, upf);
 }
 
 // `par`: launch parity of the leaf's row pass (group-aligned row pass only; its partials are double-buffered)
@@ -1451,7 +1439,7 @@ __global__ __launch_bounds__(VEC_THREADS) void k_control_lean(ModelDev md, Arena
                                                              int max_depth, HostStatus* st, int seq, int par) {
   // (standalone: the last leaf of a tree, whose control work has no next launch to ride in and sits between two draws -- the
   // operands of its merge levels are requested up front, PF)
-  control_lean<false, 8, true>(md, A, io, j, d, Emax, max_depth, st, seq, lean_src(md, par));
+  control_lean<8, true>(md, A, io, j, d, Emax, max_depth, st, seq, lean_src(md, par));
 }
 
 // ---------------------------------------------------------------------------
@@ -1610,7 +1598,7 @@ __device__ __forceinline__ void mva_control(const ModelDev& md, const ArenaDev& 
     s_rec[need_slot(qq)] = t;
   }
   __syncthreads();
-  control_lean<false, 8, false>(md, A, io, j, d, Emax, max_depth, st, seq, LeanSrc{s_rec, PART_STRIDE, 1, md.def_loc}, nt, tree, upf);
+  control_lean<8, false>(md, A, io, j, d, Emax, max_depth, st, seq, LeanSrc{s_rec, PART_STRIDE, 1, md.def_loc}, nt, tree, upf);
 }
 
 __global__ __launch_bounds__(VEC_THREADS) void k_mva_control(ModelDev md, ArenaDev A, EvalIO io, int j, int d, double Emax, int max_depth,
@@ -1870,7 +1858,6 @@ __global__ void k_draw_ctl_start(ArenaDev A, const double* __restrict__ kin_part
     else if (!c->aborted && max_depth > 0) ctl_next_direction(c, A.uniforms);
     if (st) publish_fields(c, st);
   }
-  if (A.ga_sync && threadIdx.x < GA_SYNC_WORDS) A.ga_sync[threadIdx.x] = 0u;
 }
 
 
@@ -1977,7 +1964,6 @@ __global__ __launch_bounds__(VEC_THREADS) void k_potential_update_exp(int n, con
 }
 
 #include "rows_ga_kernel.h"
-#include "rows_ga_tree.h"
 #include "rows_gb_kernel.h"
 #include "dense_adapt.h"
 #include "glm_kernel.h"

@@ -192,8 +192,8 @@ __device__ __forceinline__ void ga_tile(const double (&x)[D][RPL], uint32_t yb, 
 #define GA_MAXCHUNK 8      // the block reduce sums chunks of 8 consecutive groups (ga_bsz <= 64)
 #define GA_F_NOTAIL 1      // ga_flags, TIMING EXPERIMENTS ONLY: stop after the stream (results are wrong)
 
-// OCC: waves per SIMD the register budget is sized for (4: 128 VGPRs, 3: 168); PIPE: tiles in flight per wave (2 or 3).
-// G workgroups of W waves must all be resident: 4 OCC waves per CU >= W (G / CUs).
+// Register budget: four waves per SIMD (128 VGPRs), two tiles in flight per wave.
+// G workgroups of W waves must all be resident: 16 waves per CU >= W (G / CUs).
 struct GaArgs;
 template <int D>
 __device__ __forceinline__ void ga_tail(const GaArgs& T, int g, double (&s_acc)[4][2][D + 1], double (&s_red)[NDOT],
@@ -238,8 +238,8 @@ __device__ __forceinline__ void ga_hyper(const ModelDev& md, const QView& qv, in
 }
 
 // DX: stored columns of X per tile (D, or D - 1 = 7 when column 0 is identically 1; only with D = 8)
-template <int D, int RPL, int OCC, int PIPE, int DX = D>
-__global__ __launch_bounds__(64 * GA_MAXW, OCC) void k_rows_ga(GaArgs a) {
+template <int D, int RPL, int DX = D>
+__global__ __launch_bounds__(64 * GA_MAXW, 4) void k_rows_ga(GaArgs a) {
   constexpr int SPAN = WAVE * RPL;
   static_assert(DX == D || (D == 8 && DX == 7), "only the intercept column of an 8-column model is elided");
   typedef typename GaTileSel<DX>::type Tile;
@@ -280,7 +280,7 @@ __global__ __launch_bounds__(64 * GA_MAXW, OCC) void k_rows_ga(GaArgs a) {
     ga_hyper<D>(md, qv, fold, par, lane, hv, hp);
     const int aux_id = b - R.G;
     // (LDS lent from the block reduce's chunk buffer, which only a block's last arriver uses)
-    ga_aux<OCC>((const GaArgs*)__builtin_amdgcn_kernarg_segment_ptr(), aux_id, hv, hp, &s_cp[0][0], GA_MAXW, s_auxprog,
+    ga_aux<4>((const GaArgs*)__builtin_amdgcn_kernarg_segment_ptr(), aux_id, hv, hp, &s_cp[0][0], GA_MAXW, s_auxprog,
                 R.ga_bpart + ((int64_t)par * R.ga_nrec + R.ga_nblk + aux_id) * PART_STRIDE, 1);
     return;
   }
@@ -306,10 +306,10 @@ __global__ __launch_bounds__(64 * GA_MAXW, OCC) void k_rows_ga(GaArgs a) {
   auto tile_at = [&](int i) { return cbase + (int64_t)local_at(i) * TS; };
   const int l_last = (c2 == T) ? n - 1 : -1;                    // chunk-local index of the group's last (zero-padded) tile, if it is here
   const int n_last = (int)(ng - (int64_t)(T - 1) * SPAN);     // its valid rows
-  // PIPE tiles in flight per wave; the first ones are requested before anything else, so HBM is busy during the prologue
-  double xa[D][RPL], xb[D][RPL], xc[PIPE == 3 ? D : 1][RPL];
-  uint32_t ya = 0, yb = 0, yc = 0;
-  Tile ta, tb, tc;
+  // two tiles in flight per wave; the first ones are requested before anything else, so HBM is busy during the prologue
+  double xa[D][RPL], xb[D][RPL];
+  uint32_t ya = 0, yb = 0;
+  Tile ta, tb;
   // (a wave without tiles requests the chunk's first tile slot anyway: the layout keeps one tile of slack behind every chunk)
   if constexpr (D == 8 && RPL == 2) {
     const uint32_t voff16 = (uint32_t)lane * 16u, voff2 = (uint32_t)lane * 2u;
@@ -318,7 +318,6 @@ __global__ __launch_bounds__(64 * GA_MAXW, OCC) void k_rows_ga(GaArgs a) {
     ga_issue8(R.Xt + o1, R.y + o1 / DX, voff16, voff2, tb);
   } else {
     ga_load<D, RPL>(R, tile_at(0), lane, xa, ya);
-    if (PIPE == 3) ga_load<D, RPL>(R, tile_at(min(1, max(n - 1, 0))), lane, xb, yb);
   }
   if (lane == 0) {
 #pragma unroll
@@ -375,8 +374,8 @@ __global__ __launch_bounds__(64 * GA_MAXW, OCC) void k_rows_ga(GaArgs a) {
     }
     const int nm1 = n - 1;
     if constexpr (D == 8 && RPL == 2) {
-      // hand-counted loads: PIPE tiles in flight per wave; the requests past the end re-read the wave's last tile (an L2 hit) so that
-      // every stage has exactly 9 (PIPE - 1) younger loads behind the tile it waits for
+      // hand-counted loads: two tiles in flight per wave; the requests past the end re-read the wave's last tile (an L2 hit) so that
+      // every stage has exactly 9 younger loads behind the tile it waits for
       const uint32_t voff16 = (uint32_t)lane * 16u, voff2 = (uint32_t)lane * 2u;
       auto issue = [&](int i, Tile& t) {
         const int64_t off = tile_at(min(i, nm1));
@@ -384,51 +383,24 @@ __global__ __launch_bounds__(64 * GA_MAXW, OCC) void k_rows_ga(GaArgs a) {
       };
 #define GA_ASTAGE(T, I)                                                                      \
       {                                                                                      \
-        ga_wait8<LOADS * (PIPE - 1)>(T);                                                     \
+        ga_wait8<LOADS>(T);                                                                  \
         if ((I) == nsw) flush();                                                             \
         double xx[8][2];                                                                     \
         ga_unpack(T, xx);                                                                    \
         ga_tile<8, 2>(xx, T.y, beta, local_at(I) == l_last ? n_last : SPAN, lane, acc, lp); \
       }
-      if constexpr (PIPE == 3) {
-        issue(2, tc);
-        for (int i = 0; i < n; i += 3) {
-          GA_ASTAGE(ta, i)
-          if (i + 1 >= n) break;
-          issue(i + 3, ta);
-          GA_ASTAGE(tb, i + 1)
-          if (i + 2 >= n) break;
-          issue(i + 4, tb);
-          GA_ASTAGE(tc, i + 2)
-          issue(i + 5, tc);
-        }
-        ga_wait8<0>(ta); ga_wait8<0>(tb); ga_wait8<0>(tc);
-      } else {
-        for (int i = 0; i < n; i += 2) {
-          GA_ASTAGE(ta, i)
-          if (i + 1 >= n) break;
-          issue(i + 2, ta);
-          GA_ASTAGE(tb, i + 1)
-          issue(i + 3, tb);
-        }
-        ga_wait8<0>(ta); ga_wait8<0>(tb);
+      for (int i = 0; i < n; i += 2) {
+        GA_ASTAGE(ta, i)
+        if (i + 1 >= n) break;
+        issue(i + 2, ta);
+        GA_ASTAGE(tb, i + 1)
+        issue(i + 3, tb);
       }
+      ga_wait8<0>(ta); ga_wait8<0>(tb);
 #undef GA_ASTAGE
     } else {
-    // compiler-counted loads.  The prefetch of tile i + PIPE - 1 is UNCONDITIONAL (past the end it re-requests the wave's last tile):
-    // a load inside an `if` makes hipcc drain every outstanding load (`s_waitcnt vmcnt(0)`) at the join.
-    if constexpr (PIPE == 3) {
-      for (int i = 0; i < n; i += 3) {
-        ga_load<D, RPL>(R, tile_at(min(i + 2, nm1)), lane, xc, yc);
-        GA_STAGE(xa, ya, i)
-        if (i + 1 >= n) break;
-        ga_load<D, RPL>(R, tile_at(min(i + 3, nm1)), lane, xa, ya);
-        GA_STAGE(xb, yb, i + 1)
-        if (i + 2 >= n) break;
-        ga_load<D, RPL>(R, tile_at(min(i + 4, nm1)), lane, xb, yb);
-        GA_STAGE(xc, yc, i + 2)
-      }
-    } else {
+      // compiler-counted loads.  The prefetch of tile i + 1 is UNCONDITIONAL (past the end it re-requests the wave's last tile):
+      // a load inside an `if` makes hipcc drain every outstanding load (`s_waitcnt vmcnt(0)`) at the join.
       for (int i = 0; i < n; i += 2) {
         ga_load<D, RPL>(R, tile_at(min(i + 1, nm1)), lane, xb, yb);
         GA_STAGE(xa, ya, i)
@@ -436,7 +408,6 @@ __global__ __launch_bounds__(64 * GA_MAXW, OCC) void k_rows_ga(GaArgs a) {
         ga_load<D, RPL>(R, tile_at(min(i + 2, nm1)), lane, xa, ya);
         GA_STAGE(xb, yb, i + 1)
       }
-    }
     }
 #undef GA_STAGE
     if (n > 0) flush();

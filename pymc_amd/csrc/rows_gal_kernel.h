@@ -141,9 +141,9 @@ __device__ __forceinline__ void gal_tail_wave(const ModelDev& md, const GaLeafAr
 
 // D = 8 covariates, two rows per lane; DX stored columns (7: the intercept column is not stored).  Grid: GAL_MAXC control workgroups +
 // G group workgroups; block: NC waves, wave c = chain c of this launch.  OCC: waves per SIMD the register budget is sized for.
-template <int NC, int DX, int OCC, int PF = GAL_PF>
+template <int NC, int DX, int OCC>
 __global__ __launch_bounds__(64 * NC, OCC) void k_rows_gal(ModelDev md, const GalConst* __restrict__ konst, GalArgs<NC> la) {
-  constexpr int D = 8, SPAN = WAVE * 2, RING = PF + 1;
+  constexpr int D = 8, SPAN = WAVE * 2, PF = GAL_PF, RING = GAL_RING;
   constexpr int ITEMS = DX + 1;                              // requests of a tile: DX columns of 1 KiB + the 128 y bytes (as 64 x 4 B)
   constexpr int LPT = (ITEMS + NC - 1) / NC;                 // ... per wave (the same count in every wave: the waits are immediates)
   constexpr int SLOT = DX * 1024 + 256;                      // bytes of a ring slot
@@ -168,7 +168,7 @@ __global__ __launch_bounds__(64 * NC, OCC) void k_rows_gal(ModelDev md, const Ga
     if (L.fold & GA_FOLD_CTL) {
       UniPrefetch upf;
       uni_prefetch_none(upf);
-      control_lean_in<false, 8, false>(md, L.A, L.cio, L.cj, L.cd, L.Emax, L.max_depth, L.st, L.cseq, gam_src(R, L, L.par ^ 1),
+      control_lean_in<8, false>(md, L.A, L.cio, L.cj, L.cd, L.Emax, L.max_depth, L.st, L.cseq, gam_src(R, L, L.par ^ 1),
                                        NC * WAVE > VEC_THREADS ? VEC_THREADS : 0, false, upf, *reinterpret_cast<CtlLds*>(s_ring));
     }
     return;

@@ -84,7 +84,7 @@ __device__ __forceinline__ void gb_body(const ModelDev& md, const GbChain& a, in
   if (GB_XF(GB_F_EMPTY)) return;
   if ((fold & GA_FOLD_CTL) || !karg) {   // workgroup 0: control work, from the previous launch's block partials
     if (b == 0 && (GB_XF(GB_F_NOCTL) || !(fold & GA_FOLD_CTL))) return;
-    if (b == 0) { control_lean<false, 8, true>(md, A, a.cio, a.cj, a.cd, a.Emax, a.max_depth, a.st, a.cseq, src_of(par ^ 1), GB_W * WAVE > VEC_THREADS ? VEC_THREADS : 0); return; }
+    if (b == 0) { control_lean<8, true>(md, A, a.cio, a.cj, a.cd, a.Emax, a.max_depth, a.st, a.cseq, src_of(par ^ 1), GB_W * WAVE > VEC_THREADS ? VEC_THREADS : 0); return; }
     --b;
   }
   const int tid = threadIdx.x, lane = tid & (WAVE - 1), w = __builtin_amdgcn_readfirstlane(tid >> 6);

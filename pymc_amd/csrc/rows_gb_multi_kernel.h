@@ -17,7 +17,8 @@ struct GbmArgs { GalLeaf c[GAL_MAXC]; GalConst k[GAL_MAXC]; int nc, rev; };
 
 // OCC: waves per SIMD the register budget is sized for.  The single-chain kernel takes 175 registers (two waves per SIMD: ONE
 // workgroup of eight waves per CU -- enough for its 157 workgroups); a merged launch of c chains has 157 c workgroups and runs in
-// ceil(157 c / (256 x workgroups per CU)) rounds, so it is built for more workgroups per CU at the price of a few spilled registers.
+// ceil(157 c / (256 x workgroups per CU)) rounds.  Budgets for more workgroups per CU spilled, and the spills cost more than the
+// rounds they saved: the engine launches it at the single-chain kernel's budget.
 template <int D, int DX, int OCC>
 __global__ __launch_bounds__(64 * GB_W, OCC) void k_rows_gb_multi(ModelDev md, GbmArgs ma) {
   const int per = md.lg.ga_nblk + 1;

@@ -42,7 +42,7 @@ __device__ __forceinline__ void rows_flush(double (&acc)[D], double* __restrict_
 //
 // The row pass is bound by these few lines, not by HBM: with the library's exp / log1p / division a tile of 128 rows costs 680
 // vector instructions per wave (two thirds of them fp64 or the moves that feed `v_fmac`), 1.2 us of a SIMD, and a SIMD holding
-// three waves of 16 tiles is busy for the whole 55 us of the pass (per-workgroup timeline, tools/tree_wg_timeline.py: the
+// three waves of 16 tiles is busy for the whole 55 us of the pass (per-workgroup timeline of the former persistent tree kernel: the
 // workgroups dispatched first finish their stream after 23 us, the last after 55 us).  All three functions are needed only on
 // a narrow domain here -- e = exp(-|eta|) in (0, 1], 1 + e and 2 + e in (1, 3] -- so they are written out for that domain:
 //   exp(x), x <= 0     k = rint(x log2 e), r = x - k ln 2 (two-part), Taylor to r^13 (|r| <= 0.347: 4e-18), v_ldexp_f64
@@ -212,8 +212,7 @@ __device__ __forceinline__ void rows_hyper(const RowsDev& R, const QView& qv, in
 // `part` / `stride` / `nblk` / `def_loc`: where the previous leaf left its partial sums and local parts (kernel B's records, or
 // the block partials of the group-aligned row pass).  Lane l returns, for hyper-parameter element e = l mod 2D
 // (mu[0..D), sigma[0..D)), this leaf's q' (`val`) and p_half (`ph`).
-// AGENT: partials, local parts and the source state's q were written by other workgroups of THIS launch (rows_ga_tree.h).
-template <int D, bool AGENT = false>
+template <int D>
 __device__ __forceinline__ void rows_hyper_fold_elem(const RowsDev& R, const double* part, int stride, int nblk, const double* def_loc,
                                                      const QView& qv, int lane, double& val, double& ph) {
   constexpr int NE = 2 * D;                 // mu[0..D), sigma[0..D)
@@ -224,18 +223,9 @@ __device__ __forceinline__ void rows_hyper_fold_elem(const RowsDev& R, const dou
   const int dd = is_mu ? e : e - D;
   const int i = (is_mu ? R.off_mu : R.off_sigma) + dd;
   const int slot = (is_mu ? R.def_mu : R.def_sigma) + dd;
-  double2 l01, l23;   // {gx local, dx/dq}, {dlog|J|/dq, p_half}
-  double qi;
-  if (AGENT) {
-    const double* dl = def_loc + 4 * slot;
-    l01 = make_double2(ld_agent(dl), ld_agent(dl + 1));
-    l23 = make_double2(ld_agent(dl + 2), ld_agent(dl + 3));
-    qi = ld_agent(qv.q + i);
-  } else {
-    l01 = reinterpret_cast<const double2*>(def_loc)[2 * slot];
-    l23 = reinterpret_cast<const double2*>(def_loc)[2 * slot + 1];
-    qi = qv.q[i];
-  }
+  const double2 l01 = reinterpret_cast<const double2*>(def_loc)[2 * slot];       // {gx local, dx/dq}
+  const double2 l23 = reinterpret_cast<const double2*>(def_loc)[2 * slot + 1];   // {dlog|J|/dq, p_half}
+  const double qi = qv.q[i];
   const double vi = qv.var[i];
   const int per = (nblk + CTL_CHUNKS - 1) / CTL_CHUNKS;
   double cs[NS];
@@ -244,7 +234,7 @@ __device__ __forceinline__ void rows_hyper_fold_elem(const RowsDev& R, const dou
     const int pair = (lane + WAVE * s) % NP;
     const int pe = pair % NE, c = pair / NE;
     const int k = pe < D ? PART_DMU + pe : PART_DSG + (pe - D);
-    cs[s] = sum_strided<AGENT>(part + k, stride, c * per, min(nblk, (c + 1) * per));
+    cs[s] = sum_strided(part + k, stride, c * per, min(nblk, (c + 1) * per));
   }
   double S = 0.0;
   if constexpr (WAVE % NE == 0) {   // D a power of two: the pairs of a chunk never straddle two of the per-lane slots

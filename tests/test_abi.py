@@ -134,8 +134,8 @@ def test_streaming_kernels_hold_their_tiles_in_registers(lib, tmp_path):
     assert len(ga) >= 8, sorted(kernels)[:10]
     # the group-block pass (rows_gb_kernel.h) uses ordinary loads; it is held to the same bar because a spill inside its short
     # per-group loop would cost more than the loop itself (`k_vector`, which it replaces at C2-S, carries 144 B of scratch)
-    # (of the merged launch `k_rows_gb_multi` the default register budget only: the 128- / 80-register instantiations exist for the
-    # A/B that showed their spills cost more than the rounds they save)
+    # (the merged launch `k_rows_gb_multi` at its one register budget, two waves per SIMD: the 128- / 80-register instantiations
+    # were removed after the A/B that showed their spills cost more than the rounds they save)
     gb = {k: v for k, v in kernels.items() if re.match(r"_Z\d+k_rows_gbI", k) or re.match(r"_Z\d+k_rows_gb_multiILi\d+ELi\d+ELi2EE", k)}
     assert len(gb) >= 4, sorted(kernels)[:10]
     for name, (spills, scratch) in gb.items():

@@ -499,7 +499,7 @@ STAT_KEYS = ("depth", "tree_size", "index_in_trajectory", "diverging", "reached_
 def _run_schedule(spec, env, monkeypatch, tune, draws, seed, **step_kwargs):
     from pymc_amd.sampling import sample
 
-    keys = ("NUTS_GA_VARIANT", "NUTS_GA_TREE", "NUTS_ROWS_GA", "NUTS_XFOLD", "NUTS_SPEC_MAX", "NUTS_FOLD_CTL", "NUTS_GA_ONES0", "NUTS_MVN_ALIGNED", "NUTS_XPRE")
+    keys = ("NUTS_ROWS_GA", "NUTS_XFOLD", "NUTS_SPEC_MAX", "NUTS_FOLD_CTL", "NUTS_GA_ONES0", "NUTS_MVN_ALIGNED", "NUTS_XPRE")
     for k in keys:
         monkeypatch.delenv(k, raising=False)
     for k, v in env.items():
@@ -507,7 +507,7 @@ def _run_schedule(spec, env, monkeypatch, tune, draws, seed, **step_kwargs):
     res = sample(draws=draws, tune=tune, chains=1, model=spec, init="adapt_diag", random_seed=seed, device=0, discard_tuned_samples=False,
                  **step_kwargs)
     step = res["step"]
-    info = (step._scalar("tree_kernel"), step._scalar("tree_launches"))
+    info = (step._logp_dlogp_func.model_scalar("rows_group_aligned"), step._logp_dlogp_func.model_scalar("rows_group_block"))
     out = (np.array(res["draws"][0]), res["stats"][0], info)
     step.close()
     for k in keys:
@@ -515,23 +515,28 @@ def _run_schedule(spec, env, monkeypatch, tune, draws, seed, **step_kwargs):
     return out
 
 
+# launch-per-leaf reschedulings of the group-aligned pass that must give the default schedule's chain bit for bit
+GA_RESCHEDULINGS = ({"NUTS_FOLD_CTL": "0"}, {"NUTS_XFOLD": "0"})
+
+
 @pytest.mark.parametrize("which", ["c2s", "c2l"])
-def test_tree_kernel_is_a_pure_rescheduling(which, c2l, c2s, monkeypatch):
-    """The persistent tree kernel (csrc/rows_ga_tree.h: one launch per NUTS transition, leaf loop and doubling loop on the device,
-    counters instead of kernel boundaries) against one launch per leapfrog of the same row pass: positions and every statistic
-    BITWISE equal through tuning (trees of 1 .. 255 leaves, both directions, U-turns inside and at the end of doublings)."""
+def test_group_aligned_pass_is_a_pure_rescheduling(which, c2l, c2s, monkeypatch):
+    """The group-aligned row pass under its default schedule (control work folded into the next row pass, also across doublings)
+    against the same launches with the control work unfolded: positions and every statistic BITWISE equal through tuning (trees of
+    1 .. 255 leaves, both directions, U-turns inside and at the end of doublings)."""
     # (C2-S has ONE tile per group: the group-aligned pass is not what the engine would choose for it -- forced here, it runs the
     # kernel with a wave that has no tiles at all)
     spec, tune, draws = (c2s, 40, 20) if which == "c2s" else (c2l, 14, 6)
-    base = {"NUTS_GA_VARIANT": "32", "NUTS_ROWS_GA": "2"}
-    d0, s0, i0 = _run_schedule(spec, {**base, "NUTS_GA_TREE": "0"}, monkeypatch, tune, draws, 77)
-    d1, s1, i1 = _run_schedule(spec, {**base, "NUTS_GA_TREE": "1"}, monkeypatch, tune, draws, 77)
-    assert i0[0] == 0.0 and i1[0] == 1.0 and i1[1] == tune + draws, (i0, i1)
-    assert np.array_equal(d0, d1)
-    for a, b in zip(s0, s1):
-        for k in STAT_KEYS:
-            assert a[k] == b[k] or (a[k] != a[k] and b[k] != b[k]), (k, a[k], b[k])
-    print(f"{which}: tree sizes {[int(s['tree_size']) for s in s1]}")
+    base = {"NUTS_ROWS_GA": "2"}
+    d0, s0, i0 = _run_schedule(spec, base, monkeypatch, tune, draws, 77)
+    assert i0 == (1.0, 0.0), i0
+    for env in GA_RESCHEDULINGS:
+        d1, s1, i1 = _run_schedule(spec, {**base, **env}, monkeypatch, tune, draws, 77)
+        assert i1 == i0 and np.array_equal(d0, d1), (env, i1)
+        for a, b in zip(s0, s1):
+            for k in STAT_KEYS:
+                assert a[k] == b[k] or (a[k] != a[k] and b[k] != b[k]), (env, k, a[k], b[k])
+    print(f"{which}: tree sizes {[int(s['tree_size']) for s in s0]}")
 
 
 def test_cross_doubling_fold_is_a_pure_rescheduling(c2l, monkeypatch):
@@ -555,25 +560,26 @@ def test_cross_doubling_fold_is_a_pure_rescheduling(c2l, monkeypatch):
 
 
 @pytest.mark.parametrize("case", ["divergences", "max_treedepth"])
-def test_tree_kernel_on_trees_that_end_the_hard_way(case, c2l, monkeypatch):
-    """The persistent tree kernel where a tree does not end with a U-turn at the end of a doubling: a step size large enough to
-    diverge (nuts.py:419-435: the leaf's energy error exceeds Emax, inside a doubling) and a depth limit low enough to be reached
-    (nuts.py:218-225; the row workgroups leave after the last doubling without a verdict) -- bitwise against one launch per
-    leapfrog, divergence bookkeeping and `reached_max_treedepth` included."""
+def test_group_aligned_pass_on_trees_that_end_the_hard_way(case, c2l, monkeypatch):
+    """The group-aligned row pass of the benchmark model where a tree does not end with a U-turn at the end of a doubling: a step
+    size large enough to diverge (nuts.py:419-435: the leaf's energy error exceeds Emax, inside a doubling) and a depth limit low
+    enough to be reached (nuts.py:218-225) -- the default schedule bitwise against the same launches with the control work
+    unfolded, divergence bookkeeping and `reached_max_treedepth` included."""
     kw = {"step_scale": 40.0, "adapt_step_size": False} if case == "divergences" else {"max_treedepth": 3, "early_max_treedepth": 2}
-    base = {"NUTS_GA_VARIANT": "32", "NUTS_ROWS_GA": "2"}
-    d0, s0, i0 = _run_schedule(c2l, {**base, "NUTS_GA_TREE": "0"}, monkeypatch, 6, 6, 5, **kw)
-    d1, s1, i1 = _run_schedule(c2l, {**base, "NUTS_GA_TREE": "1"}, monkeypatch, 6, 6, 5, **kw)
-    assert i1[0] == 1.0 and i1[1] == 12
-    assert np.array_equal(d0, d1)
-    for a, b in zip(s0, s1):
-        for k in STAT_KEYS:
-            assert a[k] == b[k] or (a[k] != a[k] and b[k] != b[k]), (k, a[k], b[k])
+    base = {"NUTS_ROWS_GA": "2"}
+    d0, s0, i0 = _run_schedule(c2l, base, monkeypatch, 6, 6, 5, **kw)
+    assert i0 == (1.0, 0.0), i0
+    for env in GA_RESCHEDULINGS:
+        d1, s1, i1 = _run_schedule(c2l, {**base, **env}, monkeypatch, 6, 6, 5, **kw)
+        assert i1 == i0 and np.array_equal(d0, d1), (env, i1)
+        for a, b in zip(s0, s1):
+            for k in STAT_KEYS:
+                assert a[k] == b[k] or (a[k] != a[k] and b[k] != b[k]), (env, k, a[k], b[k])
     if case == "divergences":
-        assert any(s["diverging"] for s in s1)
+        assert any(s["diverging"] for s in s0)
     else:
-        assert any(s["reached_max_treedepth"] for s in s1[6:]) and max(int(s["depth"]) for s in s1) == 3
-    print(case, [int(s["tree_size"]) for s in s1], [bool(s["diverging"]) for s in s1])
+        assert any(s["reached_max_treedepth"] for s in s0[6:]) and max(int(s["depth"]) for s in s0) == 3
+    print(case, [int(s["tree_size"]) for s in s0], [bool(s["diverging"]) for s in s0])
 
 
 def test_row_aligned_mvnormal_pass(monkeypatch):

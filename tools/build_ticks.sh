@@ -1,6 +1,6 @@
 #!/bin/bash
 # the engine with measurement code compiled in, for the lab tools (loaded through PYMC_AMD_LIB; build/ travels to the GPU box):
-#   bash tools/build_ticks.sh            -DNUTS_KTIMING  -> build/libnuts_ticks.so     phase timestamps (tools/gb_ticks.py, tree_ticks.py)
+#   bash tools/build_ticks.sh            -DNUTS_KTIMING  -> build/libnuts_ticks.so     phase timestamps (tools/gb_ticks.py)
 #   bash tools/build_ticks.sh knockout   -DNUTS_KNOCKOUT -> build/libnuts_knockout.so  parts of k_rows_gb switched off by NUTS_GA_FLAGS (tools/gb_knockout.py)
 export PYMC_AMD_HONOUR_NUTS_ENV=1   # the NUTS_* variables reach the engine as schedule options (nuts_set_option)
 KIND=${1:-ticks}

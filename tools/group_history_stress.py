@@ -1,13 +1,12 @@
 #!/usr/bin/env python
 """Which side of `test_grouped_chains_of_the_logit_rows_are_bitwise_the_chains_alone[64-130-2-20-8]` is the one that moves?
 
-The test compares the chains ALONE (persistent tree kernel, rows_ga_tree.h) with the chain GROUP (rows_ga_multi_kernel.h) and
+The test compares the chains ALONE (rows_ga_kernel.h) with the chain GROUP (rows_ga_multi_kernel.h) and
 differed in about one run in ten of its FILE, never in a process of its own (profiles/r05p_rows_group_stress.json: there the
 chains alone were sampled once, first thing in a fresh process).  This tool replays the file's history in ONE process and samples
-the same two chains under all THREE schedules every round:
+the same two chains under both schedules every round:
 
-    tree   -- chains alone, one launch per transition      (k_tree_ga)
-    leaf   -- chains alone, one launch per leapfrog         (k_rows_ga; NUTS_GA_TREE=0)
+    leaf   -- chains alone, one launch per leapfrog         (k_rows_ga)
     group  -- the two chains as a chain group               (k_rows_ga_multi)
 
 and compares each with the first round's result of the same schedule and with the other schedules of its round.
@@ -88,8 +87,7 @@ def main():
     for r in range(rounds):
         history(level)
         got = {
-            "tree": _sample(spec, chains, False, 1, tune, draws, 17, NUTS_ROWS_GA=2),
-            "leaf": _sample(spec, chains, False, 1, tune, draws, 17, NUTS_ROWS_GA=2, NUTS_GA_TREE=0),
+            "leaf": _sample(spec, chains, False, 1, tune, draws, 17, NUTS_ROWS_GA=2),
             "group": _sample(spec, chains, True, chains, tune, draws, 17, NUTS_ROWS_GA=2),
         }
         for k, v in got.items():
@@ -98,10 +96,9 @@ def main():
             w = where(first[k], v)
             if w:
                 out["events"].append({"round": r, "what": f"{k} differs from the first round's {k}", **w})
-        for a, b in (("tree", "leaf"), ("tree", "group"), ("leaf", "group")):
-            w = where(got[a], got[b])
-            if w:
-                out["events"].append({"round": r, "what": f"{a} != {b} in this round", **w})
+        w = where(got["leaf"], got["group"])
+        if w:
+            out["events"].append({"round": r, "what": "leaf != group in this round", **w})
         print(f"round {r}: {len(out['events'])} events so far, {time.time() - t0:.0f} s", file=sys.stderr, flush=True)
     out["seconds"] = time.time() - t0
     print(json.dumps(out, indent=1))

@@ -105,7 +105,7 @@ def draw_timeline(path, tail_frac=0.5):
         tot["draws"] += 1
         tot["span"] += seg[-1][1] - seg[0][1]
         for (n0, s0, e0), (n1, s1, e1) in zip(seg, seg[1:]):
-            dom = "k_rows" in n0 or "k_mvn_aligned" in n0 or "k_tree_ga" in n0
+            dom = "k_rows" in n0 or "k_mvn_aligned" in n0
             tot["dominant" if dom else "other_kernels"] += e0 - s0
             if not dom:
                 other_by[n0[:40]] = other_by.get(n0[:40], 0.0) + (e0 - s0)
