@@ -30,23 +30,17 @@
 
 static thread_local std::string g_err;
 
-#define HIPCHK(expr)                                                                        \
+#define HIPCHK_RET(expr, text, ret)                                                         \
   do {                                                                                      \
     hipError_t _e = (expr);                                                                 \
     if (_e != hipSuccess) {                                                                 \
-      g_err = std::string(#expr) + ": " + hipGetErrorString(_e);                            \
-      return NUTS_E_HIP;                                                                    \
+      g_err = std::string(text) + ": " + hipGetErrorString(_e);                             \
+      return ret;                                                                           \
     }                                                                                       \
   } while (0)
-
-#define HIPCHK_NULL(expr)                                                                   \
-  do {                                                                                      \
-    hipError_t _e = (expr);                                                                 \
-    if (_e != hipSuccess) {                                                                 \
-      g_err = std::string(#expr) + ": " + hipGetErrorString(_e);                            \
-      return nullptr;                                                                       \
-    }                                                                                       \
-  } while (0)
+#define HIPCHK(expr) HIPCHK_RET(expr, #expr, NUTS_E_HIP)
+#define HIPCHK_NULL(expr) HIPCHK_RET(expr, #expr, nullptr)
+#define HIPCHK_FALSE(expr) HIPCHK_RET(expr, #expr, false)
 
 // Schedule options (include/nuts_mi355.h, nuts_set_option): which of several equivalent kernel schedules a model / chain created
 // from now on uses.  The library never reads the environment: whoever wants a non-default schedule (parity tests of every
@@ -130,22 +124,10 @@ struct nuts_model {
   bool g_active = false;       // the model's chain is inside a tree (its leaf launches are deposited with the group)
   int gslot = 0;               // the model's place in the group
   int n_chains = 0;            // chains created on this model
-  std::vector<int32_t> derived;   // NUTS_D_DERIVED factors (compile_spec)
   int64_t pool_extra = 0;         // doubles behind the spec's data pool: (values, seed) of every derived vector
   int64_t orphan_elems = 0, factor_elems = 0;   // elements of the factors without an owning variable / of all factors (compile_spec)
   int64_t rows_xt_len = 0, rows_y_len = 0;   // group-aligned row pass: elements of the tiled X / y copies (chain groups compare them)
-  // linear predictors (dense node 5, lin_kernel.h): per (predictor, column) the factors that read it = (offset of their adjoints in
-  // ModelDev.adj, factor size), collected by compile_spec; the device tables are built by build_lins once the data pool exists
-  struct LinUse { int64_t adj_off; int32_t size; };
-  std::vector<std::vector<std::vector<LinUse>>> lin_uses;
-  std::vector<LinDev> lins_host;
-  // what the resolved-operand sweep's tables are built from (build_sweep_fast): compile_spec's sweep lists, the data table with the
-  // derived vectors behind the spec's, the broadcast terms
-  std::vector<GSweepFactor> gsf_host;
-  std::vector<GSlot> gslots_host;
-  std::vector<nuts_data_ref> drefs_host;
-  std::vector<FactorBT> fbt_host;
-  std::vector<int32_t> bterm_var_host;
+  std::vector<LinDev> lins_host;   // linear predictors (dense node 5, lin_kernel.h) as uploaded by build_lins: launch_vector reads them per leapfrog
 
   template <typename T>
   T* keep(T* p) {
@@ -208,16 +190,37 @@ static nuts_model* group_base(nuts_group* g) {   // whose copy of (P, mu) every 
   return nullptr;
 }
 
+// the pending deposits by place in the group, not by arrival: the launch does not depend on who came first
+template <typename Leaf, int N>
+static void group_order(const Leaf* pend, int nc, int (&order)[N]) {
+  for (int a = 0; a < N; ++a) order[a] = a;
+  for (int a = 1; a < nc; ++a)
+    for (int b = a; b > 0 && pend[order[b]].slot < pend[order[b - 1]].slot; --b) std::swap(order[b], order[b - 1]);
+}
+
+// a merged launch of nc chains has been submitted: the waiting depositors go on
+static void group_submitted(nuts_group* g, int nc) {
+  g->launches[nc]++;
+  g->npend = 0;
+  g->gen.fetch_add(1, std::memory_order_release);
+}
+
+// a member chain's constant arguments of the merged row passes (rows_gal_kernel.h)
+static GalConst gal_const(const GaLeafArgs& L) {
+  GalConst k{};
+  k.A = L.A; k.A.uniforms = nullptr; k.A.log_uniforms = nullptr; k.Emax = L.Emax; k.st = L.st;
+  k.ga_part = L.ga_part; k.ga_bpart = L.ga_bpart; k.ga_ticket = L.ga_ticket; k.def_loc = L.def_loc; k.max_depth = L.max_depth; k.slot = L.slot;
+  return k;
+}
+
 static void group_flush_rows_locked(nuts_group* g);
 static void group_flush_locked(nuts_group* g) {
   const int nc = g->npend;
   if (!nc) return;
   if (g->kind >= 2) { group_flush_rows_locked(g); return; }
   const ModelDev& md = group_base(g)->md;
-  int order[GRP_MAXC];   // (by place in the group, not by arrival: the launch does not depend on who came first)
-  for (int a = 0; a < GRP_MAXC; ++a) order[a] = a;
-  for (int a = 1; a < nc; ++a)
-    for (int b = a; b > 0 && g->pend[order[b]].slot < g->pend[order[b - 1]].slot; --b) std::swap(order[b], order[b - 1]);
+  int order[GRP_MAXC];
+  group_order(g->pend, nc, order);
   if (g->cap > MVM_MAXC) {   // the wide group: matrix cores, whatever the number of chains in this launch
     MfmArgs ma;
     ma.nc = nc; ma.pad = 0;
@@ -243,9 +246,7 @@ static void group_flush_locked(nuts_group* g) {
     hipLaunchKernelGGL(k_mfm_pack, dim3((md.mv.k * MFM_MAXC + 255) / 256), dim3(256), 0, g->stream, md.mv, (const MfmChainConst*)g->konst_dev, ma, g->dpack);
     hipLaunchKernelGGL(k_mvn_mfma_multi, dim3(MFM_MAXC + md.mv.al_nwg), dim3(MFM_WAVES * WAVE), 0, g->stream, md.mv, (const ModelDev*)g->md_dev,
                        (const MfmChainConst*)g->konst_dev, ma, (const double*)g->dpack);
-    g->launches[nc]++;
-    g->npend = 0;
-    g->gen.fetch_add(1, std::memory_order_release);
+    group_submitted(g, nc);
     return;
   }
   const dim3 grid(MVM_MAXC + md.mv.al_nwg);
@@ -265,9 +266,7 @@ static void group_flush_locked(nuts_group* g) {
   if (md.mv.aligned == 8) MVM_BY_NC(8) else MVM_BY_NC(4)
 #undef MVM_BY_NC
 #undef MVM_LAUNCH
-  g->launches[nc]++;
-  g->npend = 0;
-  g->gen.fetch_add(1, std::memory_order_release);
+  group_submitted(g, nc);
 }
 
 // The merged launch of the group-aligned row pass: the base member's model (X, y, the closed-form priors), every pending chain's
@@ -277,10 +276,8 @@ static void group_flush_rows_locked(nuts_group* g) {
   const int nc = g->npend;
   const nuts_model* base = group_base(g);
   const ModelDev& md = base->md;
-  int order[GAL_MAXC];   // (by place in the group, not by arrival)
-  for (int a = 0; a < GAL_MAXC; ++a) order[a] = a;
-  for (int a = 1; a < nc; ++a)
-    for (int b = a; b > 0 && g->gpend[order[b]].slot < g->gpend[order[b - 1]].slot; --b) std::swap(order[b], order[b - 1]);
+  int order[GAL_MAXC];
+  group_order(g->gpend, nc, order);
   const int rev = base->rows_alternate ? (g->rows_flip ^= 1) : 0;
   auto gal_leaf = [&](GalLeaf& l, const GaLeafArgs& L) {
     l.io = L.io; l.cio = L.cio; l.uniforms = L.A.uniforms; l.log_uniforms = L.A.log_uniforms;
@@ -289,9 +286,7 @@ static void group_flush_rows_locked(nuts_group* g) {
   auto gal_upload_consts = [&]() {   // the chains' constant parts: uploaded when a chain is first seen (and should it ever change); stream-ordered before the launch
     for (int c = 0; c < nc; ++c) {
       const GaLeafArgs& L = g->gpend[order[c]];
-      GalConst k{};
-      k.A = L.A; k.A.uniforms = nullptr; k.A.log_uniforms = nullptr; k.Emax = L.Emax; k.st = L.st;
-      k.ga_part = L.ga_part; k.ga_bpart = L.ga_bpart; k.ga_ticket = L.ga_ticket; k.def_loc = L.def_loc; k.max_depth = L.max_depth; k.slot = L.slot;
+      const GalConst k = gal_const(L);
       if (!g->gal_konst_set[L.slot] || std::memcmp(&k, &g->gal_konst_host[L.slot], sizeof(k)) != 0) {
         g->gal_konst_host[L.slot] = k; g->gal_konst_set[L.slot] = true;
         hipMemcpyAsync(g->gal_konst_dev + L.slot, &g->gal_konst_host[L.slot], sizeof(k), hipMemcpyHostToDevice, g->stream);
@@ -305,9 +300,7 @@ static void group_flush_rows_locked(nuts_group* g) {
     for (int c = 0; c < nc; ++c) {
       const GaLeafArgs& L = g->gpend[order[c]];
       gal_leaf(ma.c[c], L);
-      GalConst& k = ma.k[c];
-      k.A = L.A; k.A.uniforms = nullptr; k.A.log_uniforms = nullptr; k.Emax = L.Emax; k.st = L.st;
-      k.ga_part = L.ga_part; k.ga_bpart = L.ga_bpart; k.ga_ticket = L.ga_ticket; k.def_loc = L.def_loc; k.max_depth = L.max_depth; k.slot = L.slot;
+      ma.k[c] = gal_const(L);
     }
     for (int c = nc; c < GAL_MAXC; ++c) { ma.c[c] = ma.c[0]; ma.k[c] = ma.k[0]; }
     ma.nc = nc; ma.rev = rev;
@@ -316,9 +309,7 @@ static void group_flush_rows_locked(nuts_group* g) {
     // unbounded 175 registers, 88 k / 114 k at 128, 58 k / 66 k at 80 -- the spills cost more than the rounds they save)
     if (md.lg.ga_dx == 7) hipLaunchKernelGGL((k_rows_gb_multi<8, 7, 2>), grid, block, 0, g->stream, md, ma);
     else hipLaunchKernelGGL((k_rows_gb_multi<8, 8, 2>), grid, block, 0, g->stream, md, ma);
-    g->launches[nc]++;
-    g->npend = 0;
-    g->gen.fetch_add(1, std::memory_order_release);
+    group_submitted(g, nc);
     return;
   }
   // Which merged launch: up to four chains the round-5 kernel (every wave all chains: 70 / 81 / 106 us at C2-L), five to eight the
@@ -351,9 +342,7 @@ static void group_flush_rows_locked(nuts_group* g) {
     if (md.lg.ga_dx == 7) GAL_BY_NC(7) else GAL_BY_NC(8)
 #undef GAL_BY_NC
 #undef GAL_LAUNCH
-    g->launches[nc]++;
-    g->npend = 0;
-    g->gen.fetch_add(1, std::memory_order_release);
+    group_submitted(g, nc);
     return;
   }
   const dim3 grid(GAM_MAXC + md.lg.G), block(WAVE * md.lg.ga_w);
@@ -374,9 +363,7 @@ static void group_flush_rows_locked(nuts_group* g) {
   if (md.lg.ga_dx == 7) GAM_BY_NC(7) else GAM_BY_NC(8)
 #undef GAM_BY_NC
 #undef GAM_LAUNCH
-  g->launches[nc]++;
-  g->npend = 0;
-  g->gen.fetch_add(1, std::memory_order_release);
+  group_submitted(g, nc);
 }
 
 // A deposit waits until the launch that carries it has been submitted -- by the partner that completes the set of chains standing
@@ -402,24 +389,15 @@ static void group_wait(nuts_group* g, unsigned mine) {
   }
 }
 
-static void group_deposit(nuts_model* m, const MvaLeafArgs& L) {
+static MvaLeafArgs* group_pend(nuts_group* g, const MvaLeafArgs&) { return g->pend; }
+static GaLeafArgs* group_pend(nuts_group* g, const GaLeafArgs&) { return g->gpend; }
+template <typename Leaf>
+static void group_deposit(nuts_model* m, const Leaf& L) {
   nuts_group* g = m->group;
   unsigned mine;
   {
     std::lock_guard<std::mutex> lk(g->mu);
-    g->pend[g->npend++] = L;
-    mine = g->gen.load(std::memory_order_relaxed);
-    if (g->npend >= g->nactive) { group_flush_locked(g); return; }
-  }
-  group_wait(g, mine);
-}
-
-static void group_deposit(nuts_model* m, const GaLeafArgs& L) {
-  nuts_group* g = m->group;
-  unsigned mine;
-  {
-    std::lock_guard<std::mutex> lk(g->mu);
-    g->gpend[g->npend++] = L;
+    group_pend(g, L)[g->npend++] = L;
     mine = g->gen.load(std::memory_order_relaxed);
     if (g->npend >= g->nactive) { group_flush_locked(g); return; }
   }
@@ -694,10 +672,30 @@ static void model_enqueue_plain(nuts_model* m, const double* q_dev, double* g_de
   else hipLaunchKernelGGL(k_control<false>, dim3(1), dim3(VEC_THREADS), 0, m->stream, m->md, A, io, 0, 0, 0.0, 0, (HostStatus*)nullptr, 0);
 }
 
+// What compile_spec leaves for the build steps that run after it (host only, a local of nuts_model_create).  `fac` is THE factor
+// table: what the device is given, and what every later build step reads -- never the spec's own.
+struct LinUse { int64_t adj_off; int32_t size; };
+struct CompiledSpec {
+  std::vector<VarDev> vars;
+  std::vector<nuts_factor> fac;          // the spec's factors; a NUTS_D_DERIVED factor has gained its value and seed operands, pad is rewritten
+  std::vector<nuts_data_ref> drefs;      // data table: the spec's vectors, then (values, seed) of every derived vector
+  std::vector<GSweepFactor> gsf;         // the adjoint sweep's factors and slots (model_dev.h GSlot)
+  std::vector<GSlot> gslots;
+  std::vector<FactorBT> fbt;             // broadcast terms per factor, and the scalar variable behind each term
+  std::vector<int32_t> bterm_var;
+  // linear predictors (dense node 5, lin_kernel.h): per (predictor, column) the factors that read it = (offset of their adjoints in
+  // ModelDev.adj, factor size); the device tables are built by build_lins once the data pool exists
+  std::vector<std::vector<std::vector<LinUse>>> lin_uses;
+  std::vector<int32_t> derived;          // NUTS_D_DERIVED factors, in factor order
+};
+
+static bool refuse(const char* msg) { g_err = msg; return false; }
+
 // "Compile" the spec: contributions per variable, broadcast terms, deferred elements, orphan factors.
-static bool compile_spec(nuts_model* m, const nuts_model_spec* s, std::vector<VarDev>& vars) {
+static bool compile_spec(nuts_model* m, const nuts_model_spec* s, CompiledSpec& cs) {
   ModelDev& md = m->md;
   const int nv = s->n_vars, nf = s->n_factors;
+  std::vector<VarDev>& vars = cs.vars;
   vars.resize(nv);
   for (int k = 0; k < nv; ++k) {
     const nuts_var& v = s->vars[k];
@@ -716,23 +714,25 @@ static bool compile_spec(nuts_model* m, const nuts_model_spec* s, std::vector<Va
     if (L.N * (int64_t)L.P > ((int64_t)1 << 31) || L.N > (int64_t)INT32_MAX) { g_err = "linear predictor: X too large"; return false; }
   }
   std::vector<std::vector<Contrib>> per_var(nv);
-  std::vector<FactorBT> fbt(std::max(nf, 1));
-  std::vector<int32_t> bterm_var, orphans;
-  std::vector<nuts_factor> fac(s->factors, s->factors + nf);   // (pad is rewritten: 1 = the factor has gathered operands)
+  std::vector<FactorBT>& fbt = cs.fbt;
+  fbt.assign(std::max(nf, 1), FactorBT{});
+  std::vector<int32_t>& bterm_var = cs.bterm_var;
+  std::vector<int32_t> orphans;
+  std::vector<nuts_factor>& fac = cs.fac;
+  fac.assign(s->factors, s->factors + nf);   // (pad is rewritten: 1 = the factor has gathered operands)
   std::vector<int32_t> csr;
   std::vector<std::pair<int, int>> gathered;   // (variable, index data id) pairs of the factor being compiled
-  std::vector<int32_t>& derived = m->derived;  // NUTS_D_DERIVED factors, in factor order
-  derived.clear();
+  std::vector<int32_t>& derived = cs.derived;
   // gathered adjoints (model_dev.h GSlot): the factors whose elements are swept once, ahead of the gathers that read the result
-  std::vector<GSweepFactor> gsf;
-  std::vector<GSlot> gslots;
+  std::vector<GSweepFactor>& gsf = cs.gsf;
+  std::vector<GSlot>& gslots = cs.gslots;
   std::vector<GLong> glong;
   int64_t adj_len = 0;
   int32_t gs_elems = 0;
   const bool gsweep_on = env_int("NUTS_GSWEEP", 1) != 0;
   std::vector<std::pair<int, int>> lin_used;   // (predictor, column) pairs of the factor being compiled (NUTS_OP_LIN operands)
-  m->lin_uses.assign(std::max(s->n_lins, 0), {});
-  for (int l = 0; l < s->n_lins; ++l) m->lin_uses[l].assign(std::max(std::min(s->lins[l].K, NUTS_LIN_MAXK), 0), {});
+  cs.lin_uses.assign(std::max(s->n_lins, 0), {});
+  for (int l = 0; l < s->n_lins; ++l) cs.lin_uses[l].assign(std::max(std::min(s->lins[l].K, NUTS_LIN_MAXK), 0), {});
   // (round 6, last session) a LARGE factor with an expression program and no owning variable -- a likelihood over data whose
   // parameters are scalars: curve fits, robust regressions written out -- is swept as well, with no slot at all: the sweep accounts
   // its log-density and its scalars' adjoints (gs_part), and the scalar-driven sweep kernel walks it at a fraction of kernel B's cost
@@ -785,7 +785,7 @@ static bool compile_spec(nuts_model* m, const nuts_model_spec* s, std::vector<Va
     }
     for (const auto& lv : lin_used) {   // a predictor column is a slot too: var = -1 - predictor, did = column (model_dev.h push)
       gslots.push_back(GSlot{-1 - lv.first, lv.second, adj_len});
-      m->lin_uses[lv.first][lv.second].push_back(nuts_model::LinUse{adj_len, (int32_t)fsize});
+      cs.lin_uses[lv.first][lv.second].push_back(LinUse{adj_len, (int32_t)fsize});
       adj_len += fsize;
     }
     gs_elems += (int32_t)fsize;
@@ -839,6 +839,20 @@ static bool compile_spec(nuts_model* m, const nuts_model_spec* s, std::vector<Va
     per_var[o.ref].push_back(cb);
     fac[fi].pad = 1;
     m->has_prog = true;
+    return true;
+  };
+  // scalar variable `ref` broadcasts into factor fi at (argument, operand slot), or anywhere in its program (-1, -1)
+  auto add_bterm = [&](int fi, int ref, int arg, int slot) -> bool {
+    int b = -1;
+    for (size_t t = 0; t < bterm_var.size(); ++t) if (bterm_var[t] == ref) b = (int)t;
+    if (b < 0) {
+      if ((int)bterm_var.size() >= MAX_BTERMS) { g_err = "too many scalar variables broadcast against vector factors (MAX_BTERMS)"; return false; }
+      b = (int)bterm_var.size();
+      bterm_var.push_back(ref);
+    }
+    if (fbt[fi].n >= MAX_FACTOR_BT) { g_err = "too many scalar operands in one factor (MAX_FACTOR_BT)"; return false; }
+    fbt[fi].e[fbt[fi].n].arg = (int16_t)arg; fbt[fi].e[fbt[fi].n].slot = (int16_t)slot; fbt[fi].e[fbt[fi].n].bterm = b;
+    fbt[fi].n++;
     return true;
   };
   for (int fi = 0; fi < nf; ++fi) {
@@ -918,16 +932,7 @@ static bool compile_spec(nuts_model* m, const nuts_model_spec* s, std::vector<Va
           per_var[o->ref].push_back(cb);
           owned_already = true;
         } else if (v.size == 1) {
-          int b = -1;
-          for (size_t t = 0; t < bterm_var.size(); ++t) if (bterm_var[t] == o->ref) b = (int)t;
-          if (b < 0) {
-            if ((int)bterm_var.size() >= MAX_BTERMS) { g_err = "too many scalar variables broadcast against vector factors (MAX_BTERMS)"; return false; }
-            b = (int)bterm_var.size();
-            bterm_var.push_back(o->ref);
-          }
-          if (fbt[fi].n >= MAX_FACTOR_BT) { g_err = "too many scalar operands in one factor (MAX_FACTOR_BT)"; return false; }
-          fbt[fi].e[fbt[fi].n].arg = -1; fbt[fi].e[fbt[fi].n].slot = -1; fbt[fi].e[fbt[fi].n].bterm = b;
-          fbt[fi].n++;
+          if (!add_bterm(fi, o->ref, -1, -1)) return false;
         } else { g_err = "variable does not broadcast against its factor"; return false; }
       }
       if (!owned_already) orphans.push_back(fi);
@@ -976,16 +981,7 @@ static bool compile_spec(nuts_model* m, const nuts_model_spec* s, std::vector<Va
           per_var[o.ref].push_back(cb);
           owned_already = true;
         } else if (v.size == 1) {
-          int b = -1;
-          for (size_t t = 0; t < bterm_var.size(); ++t) if (bterm_var[t] == o.ref) b = (int)t;
-          if (b < 0) {
-            if ((int)bterm_var.size() >= MAX_BTERMS) { g_err = "too many scalar variables broadcast against vector factors (MAX_BTERMS)"; return false; }
-            b = (int)bterm_var.size();
-            bterm_var.push_back(o.ref);
-          }
-          if (fbt[fi].n >= MAX_FACTOR_BT) { g_err = "too many scalar operands in one factor (MAX_FACTOR_BT)"; return false; }
-          fbt[fi].e[fbt[fi].n].arg = (int16_t)a; fbt[fi].e[fbt[fi].n].slot = (int16_t)sl; fbt[fi].e[fbt[fi].n].bterm = b;
-          fbt[fi].n++;
+          if (!add_bterm(fi, o.ref, a, sl)) return false;
         } else { g_err = "variable does not broadcast against its factor"; return false; }
       }
     }
@@ -1094,7 +1090,8 @@ static bool compile_spec(nuts_model* m, const nuts_model_spec* s, std::vector<Va
   md.po_fbt = put(fbt.data(), (size_t)nf * sizeof(FactorBT));
   md.po_btvar = put(bterm_var.data(), bterm_var.size() * sizeof(int32_t));
   // data table: the spec's vectors, then (values, seed) of every derived vector behind the spec's pool
-  std::vector<nuts_data_ref> drefs(s->data, s->data + s->n_data);
+  std::vector<nuts_data_ref>& drefs = cs.drefs;
+  drefs.assign(s->data, s->data + s->n_data);
   m->pool_extra = 0;
   md.n_derived = (int32_t)derived.size();
   for (size_t t = 0; t < derived.size(); ++t) {
@@ -1147,7 +1144,6 @@ static bool compile_spec(nuts_model* m, const nuts_model_spec* s, std::vector<Va
     hipMemset(md.gs_part, 0, (size_t)md.n_gs_blocks * (1 + MAX_BTERMS) * sizeof(double));
   }
   md.prog = m->keep(dev_upload(blob.data(), blob.size()));
-  m->gsf_host = gsf; m->gslots_host = gslots; m->drefs_host = drefs; m->fbt_host = fbt; m->bterm_var_host = bterm_var;
   return true;
 }
 
@@ -1156,23 +1152,24 @@ static bool compile_spec(nuts_model* m, const nuts_model_spec* s, std::vector<Va
 // rewritten to refer to those entries, and the slots' adjoint offsets sit in a table of their own.  Runs once the data pool and the
 // predictors' buffers exist.  The kernel reads the tables through the scalar unit (constant address space), one wave per 64-element
 // block of ONE factor (SwFactor.blk0); taken whenever a thread's LDS column fits (NUTS_GSWEEP_FAST = 0: the generic sweeps).
-static bool build_sweep_fast(nuts_model* m, const nuts_model_spec* s, const std::vector<VarDev>& vars) {
+static bool build_sweep_fast(nuts_model* m, const nuts_model_spec* s, const CompiledSpec& cs) {
   ModelDev& md = m->md;
   md.n_swf = 0; md.sw_bytes = 0; md.sw_rows = 0; md.sw_blob = nullptr;
   const int opt = env_int("NUTS_GSWEEP_FAST", 1);
-  if (m->gsf_host.empty() || opt == 0 || !md.pool) return true;
+  if (cs.gsf.empty() || opt == 0 || !md.pool) return true;
+  const std::vector<VarDev>& vars = cs.vars;
   std::vector<SwFactor> swf;
   std::vector<SwLeaf> leaves;
   std::vector<nuts_instr> instrs;
   std::vector<int64_t> slot_off;
   int max_leaves = 1, max_slots = 1, max_instr = 1;
-  for (const GSweepFactor& g : m->gsf_host) {
-    const nuts_factor& f = s->factors[g.f];
+  for (const GSweepFactor& g : cs.gsf) {
+    const nuts_factor& f = cs.fac[g.f];
     SwFactor F{};
     F.f = g.f; F.elem0 = g.elem0; F.size = f.size; F.orphan = g.orphan;
     F.n_instr = f.n_instr; F.nargs = f.nargs; F.dist = f.dist; F.konst = f.konst;
     F.slot0 = (int32_t)slot_off.size(); F.n_slots = g.n_slots;
-    for (int sl = 0; sl < g.n_slots; ++sl) slot_off.push_back(m->gslots_host[g.slot0 + sl].adj_off);
+    for (int sl = 0; sl < g.n_slots; ++sl) slot_off.push_back(cs.gslots[g.slot0 + sl].adj_off);
     struct Key { int kind, ref, did; };
     std::vector<Key> keys;          // leaves in order of first use
     std::vector<SwLeaf> lf;
@@ -1183,22 +1180,22 @@ static bool build_sweep_fast(nuts_model* m, const nuts_model_spec* s, const std:
       SwLeaf L{};
       int pt = -1;
       if (o.kind == NUTS_OP_DATA) {
-        const nuts_data_ref r = m->drefs_host[o.ref];
+        const nuts_data_ref r = cs.drefs[o.ref];
         L.kind = SWL_DATA; L.bcast = r.size > 1 ? 0 : 1; L.ptr = md.pool + r.offset;
       } else if (o.kind == NUTS_OP_LIN) {
         const LinDev& D = m->lins_host[o.ref];
         L.kind = SWL_DATA; L.bcast = D.N > 1 ? 0 : 1; L.ptr = D.eta + (int64_t)did * D.N;
-        for (int sl = 0; sl < g.n_slots; ++sl) { const GSlot& gs = m->gslots_host[g.slot0 + sl]; if (gs.var == -1 - o.ref && gs.did == did) { pt = sl; break; } }
+        for (int sl = 0; sl < g.n_slots; ++sl) { const GSlot& gs = cs.gslots[g.slot0 + sl]; if (gs.var == -1 - o.ref && gs.did == did) { pt = sl; break; } }
       } else if (o.kind == NUTS_OP_GATHER) {
-        const nuts_data_ref r = m->drefs_host[did];
+        const nuts_data_ref r = cs.drefs[did];
         const VarDev& v = vars[o.ref];
         L.kind = SWL_GATHER; L.bcast = 0; L.ptr = md.pool + r.offset; L.voff = v.offset; L.transform = v.transform; L.lower = v.lower; L.upper = v.upper;
-        for (int sl = 0; sl < g.n_slots; ++sl) { const GSlot& gs = m->gslots_host[g.slot0 + sl]; if (gs.var == o.ref && gs.did == did) { pt = sl; break; } }
+        for (int sl = 0; sl < g.n_slots; ++sl) { const GSlot& gs = cs.gslots[g.slot0 + sl]; if (gs.var == o.ref && gs.did == did) { pt = sl; break; } }
       } else {   // NUTS_OP_VAR
         const VarDev& v = vars[o.ref];
         L.kind = SWL_VAR; L.bcast = v.size > 1 ? 0 : 1; L.ptr = md.pool; L.voff = v.offset; L.transform = v.transform; L.lower = v.lower; L.upper = v.upper;
-        const FactorBT& bt = m->fbt_host[g.f];
-        for (int b = 0; b < bt.n; ++b) if (m->bterm_var_host[bt.e[b].bterm] == o.ref) { pt = -2 - bt.e[b].bterm; break; }
+        const FactorBT& bt = cs.fbt[g.f];
+        for (int b = 0; b < bt.n; ++b) if (cs.bterm_var[bt.e[b].bterm] == o.ref) { pt = -2 - bt.e[b].bterm; break; }
       }
       keys.push_back(Key{o.kind, o.ref, did}); lf.push_back(L); push_to.push_back(pt);
       return (int)keys.size() - 1;
@@ -1270,7 +1267,7 @@ static bool build_sweep_fast(nuts_model* m, const nuts_model_spec* s, const std:
 
 // Linear predictors (dense node 5, lin_kernel.h): X transposed, the predictors' buffers, where every coefficient lives and which
 // partial sums make up its gradient.  Runs once the data pool exists (a coefficient may be an element of a derived vector).
-static bool build_lins(nuts_model* m, const nuts_model_spec* s, const std::vector<VarDev>& vars) {
+static bool build_lins(nuts_model* m, const nuts_model_spec* s, const CompiledSpec& cs) {
   ModelDev& md = m->md;
   md.n_lins = 0; md.n_lin_targets = 0; md.lins = nullptr; md.lin_targets = nullptr; md.lin_srcs = nullptr; md.lin_gdense = nullptr;
   if (s->n_lins <= 0) return true;
@@ -1299,7 +1296,7 @@ static bool build_lins(nuts_model* m, const nuts_model_spec* s, const std::vecto
     std::vector<int32_t> coef((size_t)L.K * L.P);
     for (int k = 0; k < L.K; ++k) {
       LinCol& C = D.col[k];
-      const auto& uses = m->lin_uses[l][k];
+      const auto& uses = cs.lin_uses[l][k];
       if (uses.size() > LIN_MAXUSE) { g_err = "a linear predictor column is read by too many factors (LIN_MAXUSE)"; return false; }
       C.n_use = (int32_t)uses.size();
       for (size_t u = 0; u < uses.size(); ++u) { C.adj_off[u] = uses[u].adj_off; C.use_size[u] = uses[u].size; }
@@ -1308,7 +1305,7 @@ static bool build_lins(nuts_model* m, const nuts_model_spec* s, const std::vecto
       double* dst_base = nullptr; int64_t cbase = 0;
       if (L.var[k] >= 0) {
         if (L.var[k] >= md.n_vars) { g_err = "linear predictor refers to a missing variable"; return false; }
-        const VarDev& v = vars[L.var[k]];
+        const VarDev& v = cs.vars[L.var[k]];
         if (last >= v.size) { g_err = "linear predictor: coefficients beyond the end of their variable"; return false; }
         C.transform = v.transform; C.lower = v.lower; C.upper = v.upper;
         cbase = v.offset; dst_base = md.lin_gdense + v.offset;
@@ -1317,7 +1314,7 @@ static bool build_lins(nuts_model* m, const nuts_model_spec* s, const std::vecto
         int t = -1;
         for (int u = 0; u < md.n_derived; ++u) if (md.derived_f[u] == fi) t = u;
         if (t < 0) { g_err = "linear predictor: coefficients must be a variable or a NUTS_D_DERIVED factor"; return false; }
-        const int64_t sz = s->factors[fi].size;
+        const int64_t sz = cs.fac[fi].size;
         if (last >= sz) { g_err = "linear predictor: coefficients beyond the end of their derived vector"; return false; }
         C.transform = -1; C.lower = 0.0; C.upper = 0.0;
         cbase = md.derived_off[t]; dst_base = const_cast<double*>(md.pool) + md.derived_off[t] + sz;   // (the vector's seed follows its values)
@@ -1347,16 +1344,474 @@ static bool build_lins(nuts_model* m, const nuts_model_spec* s, const std::vecto
   return true;
 }
 
-extern "C" nuts_model* nuts_model_create(const nuts_model_spec* s) {
-  if (!s || s->n_vars <= 0) { g_err = "empty model spec"; return nullptr; }
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) {
-    g_err = "no HIP device visible: libnuts_mi355 requires an MI355X (gfx950); there is no CPU fallback";
-    return nullptr;
+// Logit rows, group-aligned / group-block layout (rows_ga_kernel.h, rows_gb_kernel.h): X in tiles per (group, wave) chunk.
+static bool build_rows_group(nuts_model* m, const nuts_model_spec* s, const std::vector<int64_t>& gptr, const std::vector<int32_t>& tile0,
+                             int64_t maxT, int W, int gpw) {
+  RowsDev& lg = m->md.lg;
+  const int n = m->md.n, D = lg.D, SPAN = WAVE * m->rows_rpl;
+  const int64_t n_tiles = tile0[lg.G];
+  lg.ga = 1; lg.ga_w = gpw ? GB_W : W;
+  lg.ga_gpw = gpw;
+  lg.ga_bsz = gpw ? gpw : (lg.G + 31) / 32;
+  lg.ga_flags = env_int("NUTS_GA_FLAGS", 0);
+  lg.ga_T_uni = 0; lg.ga_ng_uni = 0;
+  {
+    bool uni = lg.G > 0;
+    for (int g = 1; g < lg.G; ++g) uni = uni && (gptr[g + 1] - gptr[g] == gptr[1] - gptr[0]);
+    if (uni && maxT > 0) { lg.ga_T_uni = (int32_t)maxT; lg.ga_ng_uni = gptr[1] - gptr[0]; }
   }
-  auto* m = new nuts_model();
+  lg.ga_nblk = (lg.G + lg.ga_bsz - 1) / lg.ga_bsz;
+  // auxiliary workgroups (rows_aux.h): one thread per element that is not a z element
+  lg.ga_auxel = n - lg.G * D;
+  lg.ga_naux = m->ga_struct_ok == 2 ? (lg.ga_auxel + WAVE * lg.ga_w - 1) / (WAVE * lg.ga_w) : 0;
+  lg.ga_nrec = lg.ga_nblk + lg.ga_naux;
+  // chunk (g, w) = the tiles wave w of workgroup g streams, [w T_g / W, (w + 1) T_g / W) -- the split the kernel makes.  Chunks
+  // are placed one after the other with `GA_SKEW` doubles (8448 B = 33 x 256 B) between them, so consecutive chunk starts
+  // differ by an ODD multiple of 256 B modulo any power-of-two channel interleave.
+  // An intercept column (x_{i,0} = 1 for every row, SURVEY 8d's C2) carries no information: it is not stored, the tiles
+  // are [D - 1][SPAN] and the kernel multiplies by the literal 1.0 (rows_ga_kernel.h, GaTileRegs7) -- 57 B per row
+  // instead of 65 on a pass that is bound by the bytes it moves.  NUTS_GA_ONES0=0 keeps the column (A/B, tests).
+  bool ones0 = D == 8 && env_int("NUTS_GA_ONES0", 1) != 0 && lg.N > 0;
+  for (int64_t i = 0; ones0 && i < lg.N; ++i) ones0 = s->rows_X[i * D] == 1.0;
+  const int DX = ones0 ? D - 1 : D;
+  lg.ga_dx = DX;
+  // (the skew between chunks is an ODD multiple of 256 B and a multiple of the tile's column count, so that the y bytes
+  // of a tile sit at its element offset / DX)
+  const int64_t TS = (int64_t)DX * SPAN, GA_SKEW = env_int("NUTS_GA_SKEW", DX == 7 || DX == 5 ? 1120 : 1056);   // 32 x 35, 32 x 33
+  if (GA_SKEW % DX != 0) return refuse("NUTS_GA_SKEW must be a multiple of the stored column count");
+  std::vector<int64_t> coff((size_t)lg.G * W, 0);
+  int64_t pos = 0, max_ct = 0;
+  for (int g = 0; g < lg.G; ++g) {
+    const int64_t T = tile0[g + 1] - tile0[g];
+    for (int w = 0; w < W; ++w) {
+      const int64_t ct = (int64_t)(w + 1) * T / W - (int64_t)w * T / W;
+      coff[(size_t)g * W + w] = pos;
+      pos += ct * TS + GA_SKEW;
+      max_ct = std::max(max_ct, ct);
+    }
+  }
+  lg.ga_cstride_uni = 0;
+  if (lg.ga_T_uni > 0 && lg.ga_T_uni % W == 0) {   // equal chunks: offsets follow from the chunk index
+    lg.ga_cstride_uni = (lg.ga_T_uni / W) * TS + GA_SKEW;
+  } else lg.ga_T_uni = 0;
+  lg.Npad = n_tiles * SPAN; lg.n_spans = n_tiles;
+  // (one tile of slack at the end: a wave without tiles still issues its unconditional first request)
+  std::vector<double> xt((size_t)(pos + TS), 0.0);
+  std::vector<int8_t> yy((size_t)(pos / DX + 2 * SPAN), 0);
+  for (int g = 0; g < lg.G; ++g) {
+    const int64_t T = tile0[g + 1] - tile0[g];
+    for (int64_t i = gptr[g]; i < gptr[g + 1]; ++i) {
+      const int64_t r = i - gptr[g], t = r / SPAN, rr = r % SPAN;
+      int w = (int)(((t + 1) * W - 1) / std::max<int64_t>(T, 1));          // the wave whose range [w T / W, (w + 1) T / W) holds tile t
+      while (w > 0 && (int64_t)w * T / W > t) --w;
+      while (w + 1 < W && (int64_t)(w + 1) * T / W <= t) ++w;
+      const int64_t base = coff[(size_t)g * W + w] + (t - (int64_t)w * T / W) * TS;
+      for (int d = D - DX; d < D; ++d) xt[(size_t)(base + (int64_t)(d - (D - DX)) * SPAN + rr)] = s->rows_X[i * D + d];
+      yy[(size_t)(base / DX + rr)] = s->rows_y[i];
+    }
+  }
+  lg.Xt = m->keep(dev_upload(xt.data(), xt.size()));
+  lg.y = m->keep(dev_upload(yy.data(), yy.size()));
+  m->rows_xt_len = (int64_t)xt.size(); m->rows_y_len = (int64_t)yy.size();
+  lg.ga_coff = m->keep(dev_upload(coff.data(), coff.size()));
+  lg.ga_tile0 = m->keep(dev_upload(tile0.data(), tile0.size()));
+  lg.ga_part = m->keep(dev_alloc<double>((size_t)lg.G * PART_STRIDE));
+  // (group-block pass: slot-major, every slot padded to a multiple of 64 records -- the padding stays zero)
+  const size_t bpart_len = gpw ? 2 * (size_t)PART_STRIDE * ((lg.ga_nrec + WAVE - 1) / WAVE * WAVE) : 2 * (size_t)lg.ga_nrec * PART_STRIDE;
+  lg.ga_bpart = m->keep(dev_alloc<double>(bpart_len));
+  lg.ga_ticket = m->keep(dev_alloc<unsigned>(lg.ga_nblk));
+  if (lg.ga_part) hipMemset(lg.ga_part, 0, (size_t)lg.G * PART_STRIDE * sizeof(double));
+  if (lg.ga_bpart) hipMemset(lg.ga_bpart, 0, bpart_len * sizeof(double));
+  if (lg.ga_ticket) hipMemset(lg.ga_ticket, 0, lg.ga_nblk * sizeof(unsigned));
+  m->rows_grid = gpw ? lg.ga_nblk : lg.G;
+  return true;
+}
+
+// Logit rows, span-partitioned layout (rows_kernel.h).
+static bool build_rows_spans(nuts_model* m, const nuts_model_spec* s, int cus) {
+  RowsDev& lg = m->md.lg;
+  const int D = lg.D, SPAN = WAVE * m->rows_rpl;
+  const int32_t* gid = s->rows_gid;
+  // 16 waves per CU are resident at a time (4 per SIMD at 113 VGPRs); two such sets of shorter waves balance the
+  // tail better than one (measured with the folded control: 61.3 us per pass vs 63.0 us at 16, 62.8 at 48, 65.8 at 64)
+  // -- for passes long enough to give every wave a few spans (C2-L: 4.8 per wave); shorter, cache-resident passes are
+  // better off with one set (R = 800 rows per group: 23.5 us at 16 vs 26.2 us at 32)
+  int wpc = env_int("NUTS_ROWS_WAVES_PER_CU", 0);
+  if (wpc <= 0) {
+    const int64_t spans = (s->rows_N + (int64_t)WAVE * m->rows_rpl - 1) / ((int64_t)WAVE * m->rows_rpl);
+    wpc = spans >= (int64_t)cus * 32 * 4 ? 32 : 16;
+  }
+  // HBM layout: X in span tiles [n_spans][D][SPAN] (one contiguous block per wave-iteration, each column a
+  // coalesced 16 B/lane load), y int8, group structure as G+1 row pointers (rows are sorted by group)
+  {
+    std::vector<double> xt((size_t)D * lg.Npad, 0.0);
+    for (int64_t i = 0; i < lg.N; ++i) {
+      const int64_t sp = i / SPAN, r = i % SPAN;
+      for (int d = 0; d < D; ++d) xt[((size_t)sp * D + d) * SPAN + r] = s->rows_X[i * D + d];
+    }
+    lg.Xt = m->keep(dev_upload(xt.data(), xt.size()));
+  }
+  std::vector<int8_t> yy(lg.Npad, 0);
+  for (int64_t i = 0; i < lg.N; ++i) yy[i] = s->rows_y[i];
+  lg.y = m->keep(dev_upload(yy.data(), yy.size()));
+  const int waves_per_block = ROWS_BLOCK / WAVE;
+  int64_t want_waves = std::min<int64_t>((int64_t)cus * wpc, lg.n_spans);
+  const int nb_main = (int)((want_waves + waves_per_block - 1) / waves_per_block);
+  lg.n_waves = nb_main * waves_per_block;
+  // static tables.  A span that lies entirely inside one group is "uniform" (streamed by the main waves);
+  // the others (group boundary or padding rows inside) are "mixed" and get one wave each.
+  std::vector<int32_t> span_gid(lg.n_spans), mixed_g0, mixed_seg_base, mixed_seg_gid;
+  std::vector<int64_t> mixed_span;
+  for (int64_t sp = 0; sp < lg.n_spans; ++sp) {
+    const int64_t r0 = sp * SPAN, r1 = r0 + SPAN;
+    if (r1 <= lg.N && gid[r0] == gid[r1 - 1]) { span_gid[sp] = gid[r0]; continue; }
+    span_gid[sp] = -1;
+    mixed_span.push_back(sp);
+    mixed_g0.push_back(gid[r0]);
+    mixed_seg_base.push_back((int32_t)mixed_seg_gid.size());
+    int prev = -1;
+    for (int64_t r = r0; r < std::min<int64_t>(r1, lg.N); ++r)
+      if (gid[r] != prev) { prev = gid[r]; mixed_seg_gid.push_back(prev); }
+  }
+  lg.n_mixed = (int32_t)mixed_span.size();
+  lg.n_mixed_seg = (int32_t)mixed_seg_gid.size();
+  std::vector<int32_t> run_ptr(lg.n_waves + 1, 0), seg_gid;
+  std::vector<int4> runs;
+  for (int w = 0; w < lg.n_waves; ++w) {
+    const int64_t s0 = (int64_t)w * lg.n_spans / lg.n_waves, s1 = (int64_t)(w + 1) * lg.n_spans / lg.n_waves;
+    run_ptr[w] = (int32_t)runs.size();
+    for (int64_t sp = s0; sp < s1; ++sp) {
+      if (span_gid[sp] < 0) continue;
+      // runs of the same group inside one wave share a segment even when a mixed span sits between them
+      if (!runs.empty() && (int)runs.size() > run_ptr[w] && runs.back().z == span_gid[sp] && runs.back().x + runs.back().y == sp) {
+        runs.back().y++;
+        continue;
+      }
+      int4 r; r.x = (int)sp; r.y = 1; r.z = span_gid[sp]; r.w = (int)seg_gid.size();
+      runs.push_back(r);
+      seg_gid.push_back(span_gid[sp]);
+    }
+  }
+  run_ptr[lg.n_waves] = (int32_t)runs.size();
+  lg.n_seg = (int32_t)seg_gid.size();
+  auto group_ptr = [&](const std::vector<int32_t>& sg) {
+    std::vector<int32_t> p(lg.G + 1, 0);
+    for (int32_t g : sg) p[g + 1]++;
+    for (int g = 0; g < lg.G; ++g) p[g + 1] += p[g];
+    return p;
+  };
+  // segments are emitted in row order and rows are sorted by group => the segments of a group are contiguous
+  const std::vector<int32_t> gsp = group_ptr(seg_gid), gmp = group_ptr(mixed_seg_gid);
+  // fixed-slot segment layout (model_dev.h) when every group has few main segments and kernel B runs one element per
+  // thread: slot = group * segK + ordinal of the segment inside its group
+  int kmain = 1;
+  for (int g = 0; g < lg.G; ++g) kmain = std::max(kmain, gsp[g + 1] - gsp[g]);
+  lg.segK = 0;
+  if (kmain <= SEG_MAIN_MAX && m->ept == 1 && env_int("NUTS_SEG_FIXED", 1)) {
+    lg.segK = kmain + 2;
+    for (auto& r : runs) r.w = r.z * lg.segK + (r.w - gsp[r.z]);
+  }
+  const size_t seg_doubles = lg.segK ? (size_t)lg.G * lg.segK * D : (size_t)lg.n_seg * D;
+  lg.run_ptr = m->keep(dev_upload(run_ptr.data(), run_ptr.size()));
+  lg.runs = m->keep(dev_upload(runs.data(), runs.size()));
+  lg.gseg_ptr = m->keep(dev_upload(gsp.data(), gsp.size()));
+  lg.seg_part = m->keep(dev_alloc<double>(std::max<size_t>(seg_doubles, 1)));
+  if (lg.seg_part) hipMemset(lg.seg_part, 0, std::max<size_t>(seg_doubles, 1) * sizeof(double));
+  lg.mixed_span = m->keep(dev_upload(mixed_span.data(), mixed_span.size()));
+  lg.mixed_g0 = m->keep(dev_upload(mixed_g0.data(), mixed_g0.size()));
+  lg.mixed_seg_base = m->keep(dev_upload(mixed_seg_base.data(), mixed_seg_base.size()));
+  lg.gmix_ptr = m->keep(dev_upload(gmp.data(), gmp.size()));
+  lg.mixed_part = m->keep(dev_alloc<double>((size_t)lg.n_mixed_seg * D));
+  lg.wave_lp = m->keep(dev_alloc<double>((size_t)lg.n_waves + lg.n_mixed));
+  m->rows_grid = nb_main + (lg.n_mixed + waves_per_block - 1) / waves_per_block;
+  return true;
+}
+
+// Logit-rows node: shapes, the group structure, which row pass the model takes and that pass's layout.
+static bool build_rows(nuts_model* m, const nuts_model_spec* s, int cus) {
   ModelDev& md = m->md;
-  HIPCHK_NULL(hipStreamCreateWithFlags(&m->stream, hipStreamNonBlocking));
+  if (s->rows_N <= 0) return true;
+  const int n = md.n;
+  const int D = s->rows_D;
+  if (D < 1 || D > LOGIT_MAXD) return refuse("logit rows: 1 <= D <= 8 covariates");
+  // (D = 2, 4, 8 have every schedule; the other widths run the span-partitioned pass and the group-block pass, one element per
+  // thread in kernel B)
+  const bool d_pow2 = D == 8 || D == 4 || D == 2;
+  if (!d_pow2 && m->ept != 1) return refuse("logit rows: D must be 2, 4 or 8 for models beyond 65 536 parameters");
+  RowsDev& lg = md.lg;
+  md.has_logit = 1;
+  // launch geometry (tunable for experiments; defaults chosen from measurements)
+  m->rows_rpl = 2;
+  m->rows_alternate = env_int("NUTS_ROWS_ALTERNATE", 1) ? 1 : 0;
+  m->rows_occ = 4;
+  const int SPAN = WAVE * m->rows_rpl;
+  lg.N = s->rows_N; lg.D = D; lg.G = s->rows_G;
+  lg.Npad = (lg.N + SPAN - 1) / SPAN * SPAN;
+  lg.n_spans = lg.Npad / SPAN;
+  const nuts_var &vmu = s->vars[s->rows_mu], &vsg = s->vars[s->rows_sigma], &vz = s->vars[s->rows_z];
+  if (vmu.size != D || vsg.size != D || vz.size != (int64_t)lg.G * D || vmu.transform != NUTS_TR_NONE ||
+      vz.transform != NUTS_TR_NONE || !(vsg.transform == NUTS_TR_NONE || vsg.transform == NUTS_TR_LOG))
+    return refuse("logit rows: mu/sigma/z shapes or transforms unsupported");
+  lg.off_mu = vmu.offset; lg.off_sigma = vsg.offset; lg.off_z = vz.offset; lg.sigma_tr = vsg.transform;
+  lg.var_mu = s->rows_mu; lg.var_sigma = s->rows_sigma; lg.var_z = s->rows_z;
+  std::vector<int64_t> gptr(lg.G + 1, 0);
+  const int32_t* gid = s->rows_gid;
+  for (int64_t i = 0; i < lg.N; ++i) {
+    if (i > 0 && gid[i] < gid[i - 1]) return refuse("logit rows: group ids must be sorted");
+    if (gid[i] < 0 || gid[i] >= lg.G) return refuse("logit rows: group id out of range");
+    gptr[gid[i] + 1] = i + 1;
+  }
+  for (int g = 0; g < lg.G; ++g) gptr[g + 1] = std::max(gptr[g + 1], gptr[g]);  // empty groups
+  lg.gptr = m->keep(dev_upload(gptr.data(), gptr.size()));
+  // ---- group-aligned row pass (rows_ga_kernel.h)?  NUTS_ROWS_GA: 0 never, 1 when the shape suits it (default), 2 whenever
+  // the model structure allows it (tests: ragged / empty / tiny groups through the same kernel) ----
+  const int want = (s->rows_opts & NUTS_ROWS_NO_GROUP_ALIGNED) ? 0 : env_int("NUTS_ROWS_GA", 1);
+  std::vector<int32_t> tile0(lg.G + 1, 0);
+  int64_t maxT = 0;
+  for (int g = 0; g < lg.G; ++g) {
+    const int64_t T = (gptr[g + 1] - gptr[g] + SPAN - 1) / SPAN;
+    maxT = std::max(maxT, T);
+    tile0[g + 1] = tile0[g] + (int32_t)T;
+  }
+  const int64_t n_tiles = tile0[lg.G];
+  int W = std::min(GA_MAXW, (16 * cus) / std::max(lg.G, 1));   // all G workgroups resident at once (4 waves per SIMD, 16 per CU)
+  if (env_int("NUTS_ROWS_GA_W", 0) > 0) W = std::max(1, std::min(GA_MAXW, env_int("NUTS_ROWS_GA_W", 0)));
+  const double meanT = (double)n_tiles / std::max(lg.G, 1);
+  bool use = false;
+  if (want >= 2) { use = m->ga_struct_ok && m->ept == 1; W = std::max(1, W); }
+  else if (want == 1) use = m->ga_struct_ok && m->ept == 1 && W >= 1 && lg.G >= 2 * cus && meanT >= 4.0 * W && (double)maxT <= 1.5 * meanT + 1.0;
+  // group-BLOCK pass (rows_gb_kernel.h) for small groups: the same closed-form model, a workgroup owns GPW whole groups and
+  // nothing crosses workgroups inside the launch.  NUTS_ROWS_GB=0 keeps such models on the general path (A/B, tests).
+  int gpw = 0;
+  if (!use && want == 1 && !(s->rows_opts & NUTS_ROWS_NO_GROUP_BLOCK) && env_int("NUTS_ROWS_GB", 1) && m->ga_struct_ok && m->ept == 1 &&
+      lg.G >= 64 && maxT <= 16) {
+    gpw = GB_W * (int)((lg.G + GB_W * 512 - 1) / (GB_W * 512));   // a group per wave; more (in sequence) only to stay <= 512 workgroups
+    gpw = std::min(gpw, GB_MAXGPW);
+    if (env_int("NUTS_ROWS_GPW", 0) > 0) gpw = std::max(1, std::min(GB_MAXGPW, env_int("NUTS_ROWS_GPW", 0)));
+    // (slot_sum: at most SLOT_SUM_MAXR records per lane -- block partials + the records of the auxiliary workgroups)
+    const int aux_threads = WAVE * GB_W, auxel = n - lg.G * D;
+    const int naux = m->ga_struct_ok == 2 ? (auxel + aux_threads - 1) / aux_threads : 0;
+    if ((lg.G + gpw - 1) / gpw + naux > WAVE * SLOT_SUM_MAXR) gpw = 0;
+  }
+  if (gpw) { use = true; W = 1; }   // (layout: one chunk per group)
+  const bool group = use && n_tiles * (int64_t)SPAN < ((int64_t)1 << 31) && (gpw || lg.G <= 32 * 8 * GA_MAXCHUNK);
+  if (!(group ? build_rows_group(m, s, gptr, tile0, maxT, W, gpw) : build_rows_spans(m, s, cus))) return false;
+  m->alg_bytes += lg.N * (8 * (int64_t)D + 1 + 4);  // X row + y + group id per row
+  return true;
+}
+
+// MvNormal node (kernels.h k_mvn_matvec / k_mvn_aligned).
+static bool build_mvn(nuts_model* m, const nuts_model_spec* s) {
+  ModelDev& md = m->md;
+  if (s->mvn_k <= 0) return true;
+  const int n = md.n;
+  md.has_mvn = 1;
+  m->explicit_pre = 1;
+  MvnDev& mv = md.mv;
+  mv.k = s->mvn_k; mv.off = s->vars[s->mvn_var].offset;
+  mv.mu = m->keep(dev_upload(s->mvn_mu, mv.k));
+  mv.prec = m->keep(dev_upload(s->mvn_prec, (size_t)mv.k * mv.k));
+  mv.rowq = m->keep(dev_alloc<double>(mv.k));
+  mv.gdense = m->keep(dev_alloc<double>(n));
+  hipMemset(mv.gdense, 0, n * sizeof(double));
+  mv.konst = -0.5 * mv.k * std::log(2.0 * M_PI) - s->mvn_logdet;
+  mv.winv = nullptr; mv.winv_t = nullptr; mv.wy = nullptr;
+  if (s->mvn_winv) {   // "cholesky" solver (include/nuts_mi355.h): W and W^T row-major, so that both mat-vecs read rows
+    const size_t kk = (size_t)mv.k * mv.k;
+    std::vector<double> wt(kk);
+    for (int r = 0; r < mv.k; ++r)
+      for (int cc = 0; cc < mv.k; ++cc) wt[(size_t)cc * mv.k + r] = s->mvn_winv[(size_t)r * mv.k + cc];
+    mv.winv = m->keep(dev_upload(s->mvn_winv, kk));
+    mv.winv_t = m->keep(dev_upload(wt.data(), kk));
+    mv.wy = m->keep(dev_alloc<double>(3 * (size_t)mv.k));
+  }
+  m->mvn_grid = mv.k;   // one workgroup per row
+  m->alg_bytes += 8 * (int64_t)mv.k * mv.k;
+  // the model IS this node (one untransformed vector variable, no other factor): the row-aligned pass finishes the leapfrog
+  // in the mat-vec's own workgroups (kernels.h, k_mvn_aligned)
+  mv.aligned = 0; mv.al_nwg = 0; mv.al_part = nullptr;
+  if (md.lean_ok && !md.has_logit && !mv.winv && mv.off == 0 && mv.k == n && s->n_vars == 1 && s->n_factors == 0 &&
+      s->vars[0].transform == NUTS_TR_NONE && md.n_deferred == 0 && md.n_orphans == 0) {
+    // rows per workgroup; 0: the two-kernel leapfrog.  Fewer, larger workgroups = fewer records for the control work to total and
+    // a cheaper launch: at k = 2048 (C3) 8 rows measured 120 k leapfrog/s against 108 k with 4 and 88 k with 2
+    const int R = env_int("NUTS_MVN_ALIGNED", mv.k >= 1024 ? 8 : 4);
+    if (R == 2 || R == 4 || R == 8 || R == 16) {
+      mv.aligned = R;
+      mv.al_nwg = (mv.k + R - 1) / R;
+      mv.al_part = m->keep(dev_alloc<double>(2 * (size_t)MVA_RS * mv.al_nwg));
+      if (mv.al_part) hipMemset(mv.al_part, 0, 2 * (size_t)MVA_RS * mv.al_nwg * sizeof(double));
+    }
+  }
+  return true;
+}
+
+// Mixture node (mixture_kernel.h).
+static bool build_mix(nuts_model* m, const nuts_model_spec* s, const CompiledSpec& cs) {
+  ModelDev& md = m->md;
+  md.has_mix = 0;
+  if (s->mix_N <= 0) return true;
+  const int n = md.n;
+  const std::vector<VarDev>& vars = cs.vars;
+  MixDev& mx = md.mix;
+  if (s->rows_N > 0 || s->mvn_k > 0) return refuse("mixture node: not together with another dense node");
+  if (s->mix_K < 1 || s->mix_K > MIX_MAXK) return refuse("mixture node: 1 <= K <= 16 components");
+  if (!s->mix_y) return refuse("mixture node: no observations");
+  auto var_ok = [&](int v) { return v >= 0 && v < s->n_vars && s->vars[v].size == s->mix_K && !vars[v].deferred; };
+  if (!var_ok(s->mix_mu)) return refuse("mixture node: mu must be a variable with K elements (not a scalar that broadcasts into another factor)");
+  if (s->mix_sigma >= 0 && (!var_ok(s->mix_sigma) || (s->vars[s->mix_sigma].transform != NUTS_TR_NONE && s->vars[s->mix_sigma].transform != NUTS_TR_LOG)))
+    return refuse("mixture node: sigma must be a variable with K elements, untransformed or log-transformed");
+  if (s->mix_sigma < 0 && !s->mix_sigma_const) return refuse("mixture node: sigma is neither a variable nor a constant");
+  if (s->mix_w_simplex) {
+    const int v = s->mix_w_logits;
+    if (s->mix_K < 3 || v < 0 || v >= s->n_vars || s->vars[v].size != s->mix_K - 1 || vars[v].deferred || s->vars[v].transform != NUTS_TR_NONE || !s->mix_w_alpha)
+      return refuse("mixture node: Dirichlet weights are a variable of K - 1 elements (the simplex-transformed value, K >= 3) with K concentrations");
+    for (int k = 0; k < s->mix_K; ++k)
+      if (!(s->mix_w_alpha[k] > 0)) return refuse("mixture node: Dirichlet concentrations a > 0");   // multivariate.py Dirichlet.logp check_parameters
+  } else
+  if (s->mix_w_logits >= 0 && (!var_ok(s->mix_w_logits) || s->vars[s->mix_w_logits].transform != NUTS_TR_NONE))
+    return refuse("mixture node: the weight logits must be an untransformed variable with K elements");
+  if (s->mix_w_logits < 0 && !s->mix_w_const) return refuse("mixture node: the weights are neither softmax(logits) nor constants");
+  if (s->vars[s->mix_mu].transform != NUTS_TR_NONE) return refuse("mixture node: mu must be untransformed");
+  if (s->mix_assign >= s->n_data || (s->mix_assign >= 0 && s->data[s->mix_assign].size != s->mix_N))
+    return refuse("mixture node: one assignment per observed row");
+  mx.N = s->mix_N; mx.K = s->mix_K;
+  mx.off_mu = s->vars[s->mix_mu].offset;
+  mx.off_sigma = s->mix_sigma >= 0 ? s->vars[s->mix_sigma].offset : -1;
+  mx.tr_sigma = s->mix_sigma >= 0 ? s->vars[s->mix_sigma].transform : NUTS_TR_NONE;
+  mx.off_w = s->mix_w_logits >= 0 ? s->vars[s->mix_w_logits].offset : -1;
+  for (int k = 0; k < MIX_MAXK; ++k) { mx.sigma_c[k] = 1.0; mx.logw_c[k] = 0.0; mx.alpha[k] = 1.0; }
+  mx.w_simplex = s->mix_w_simplex ? 1 : 0; mx.pad_ = 0; mx.w_konst = 0.0;
+  if (mx.w_simplex) {
+    double sa = 0.0, sl = 0.0;
+    for (int k = 0; k < mx.K; ++k) { mx.alpha[k] = s->mix_w_alpha[k]; sa += mx.alpha[k]; sl += std::lgamma(mx.alpha[k]); }
+    mx.w_konst = std::lgamma(sa) - sl + std::log((double)mx.K);
+  }
+  if (s->mix_sigma < 0)
+    for (int k = 0; k < mx.K; ++k) {
+      if (!(s->mix_sigma_const[k] > 0)) return refuse("mixture node: sigma > 0");   // continuous.py:532 check_parameters
+      mx.sigma_c[k] = s->mix_sigma_const[k];
+    }
+  if (s->mix_w_logits < 0) {
+    double sum = 0.0;
+    for (int k = 0; k < mx.K; ++k) { if (!(s->mix_w_const[k] >= 0 && s->mix_w_const[k] <= 1)) return refuse("mixture node: 0 <= weights <= 1, sum(weights) == 1"); sum += s->mix_w_const[k]; }
+    if (std::fabs(sum - 1.0) > 1e-8) return refuse("mixture node: 0 <= weights <= 1, sum(weights) == 1");   // mixture.py:487-493
+    for (int k = 0; k < mx.K; ++k) mx.logw_c[k] = std::log(s->mix_w_const[k]);
+  }
+  mx.y = m->keep(dev_upload(s->mix_y, (size_t)s->mix_N));
+  mx.assign = s->mix_assign >= 0 ? md.pool + s->data[s->mix_assign].offset : nullptr;
+  mx.nwg = (int)std::max<int64_t>(1, std::min<int64_t>(512, (s->mix_N + 4 * MIX_BLOCK - 1) / (4 * MIX_BLOCK)));
+  mx.part = m->keep(dev_alloc<double>((size_t)mx.nwg * (3 * MIX_MAXK + 1)));
+  mx.gdense = m->keep(dev_alloc<double>((size_t)n + 1));
+  mx.lp = mx.gdense + n;
+  if (mx.part) hipMemset(mx.part, 0, (size_t)mx.nwg * (3 * MIX_MAXK + 1) * sizeof(double));
+  if (mx.gdense) hipMemset(mx.gdense, 0, ((size_t)n + 1) * sizeof(double));
+  md.has_mix = 1;
+  m->alg_bytes += 8 * s->mix_N + (s->mix_assign >= 0 ? 8 * s->mix_N : 0);
+  return true;
+}
+
+// GLM node (glm_kernel.h).
+static bool build_glm(nuts_model* m, const nuts_model_spec* s, const CompiledSpec& cs, int cus) {
+  ModelDev& md = m->md;
+  md.has_glm = 0;
+  if (s->glm_N <= 0) return true;
+  const int n = md.n;
+  GlmDev& gm = md.glm;
+  if (s->rows_N > 0 || s->mix_N > 0) return refuse("GLM node: together with an MvNormal node only, not with the logit rows or the mixture node");
+  if (s->mvn_k > 0 && s->mvn_winv) return refuse("GLM node next to an MvNormal node: the MvNormal node's precision solver only");
+  if (s->glm_P < 1 || s->glm_P > NUTS_GLM_MAXP) return refuse("GLM node: 1 <= P <= 512 covariates");
+  if (!s->glm_X || !s->glm_y) return refuse("GLM node: no design matrix / observations");
+  if (s->glm_family < NUTS_GLM_NORMAL || s->glm_family > NUTS_GLM_POISSON) return refuse("GLM node: unknown family");
+  const int vb = s->glm_beta;
+  int dslot = -1;   // beta a derived vector: its place in the model's list of derived vectors
+  if (vb < 0) {
+    for (int t = 0; t < md.n_derived; ++t) if (md.derived_f[t] == s->glm_beta_derived) dslot = t;
+    if (dslot < 0 || cs.fac[s->glm_beta_derived].size != s->glm_P) return refuse("GLM node: glm_beta_derived must name a NUTS_D_DERIVED factor of P elements");
+  } else if (vb >= s->n_vars || s->vars[vb].size != s->glm_P || s->vars[vb].transform != NUTS_TR_NONE)
+    return refuse("GLM node: beta must be an untransformed variable with P elements (or a derived vector)");
+  auto scalar_ok = [&](int v, bool log_ok) {
+    return v >= 0 && v < s->n_vars && s->vars[v].size == 1 && (s->vars[v].transform == NUTS_TR_NONE || (log_ok && s->vars[v].transform == NUTS_TR_LOG));
+  };
+  if (s->glm_intercept >= 0 && !scalar_ok(s->glm_intercept, false)) return refuse("GLM node: the intercept must be an untransformed scalar variable");
+  if (s->glm_family == NUTS_GLM_NORMAL) {
+    if (s->glm_sigma >= 0 && !scalar_ok(s->glm_sigma, true)) return refuse("GLM node: sigma must be a scalar variable, untransformed or log-transformed");
+    if (s->glm_sigma < 0 && !(s->glm_sigma_const > 0)) return refuse("GLM node: sigma > 0");   // continuous.py:532 check_parameters
+  } else if (s->glm_sigma >= 0) return refuse("GLM node: only the Normal family has a sigma");
+  gm.N = s->glm_N; gm.P = s->glm_P; gm.family = s->glm_family;
+  // register layout: a row in the lanes of a group of `lpr`, `ch` 16-byte chunks per lane (glm_kernel.h)
+  int lpr = 1;
+  while (8 * lpr < gm.P) lpr *= 2;
+  int ch = (gm.P + 2 * lpr - 1) / (2 * lpr);
+  if (lpr == 1) ch = ch == 3 ? 4 : ch;       // instantiated: 1, 2, 4
+  else if (lpr < 32) ch = 4;                 // 4 only
+  else ch = std::max(ch, 3);                 // 3 or 4
+  gm.lpr = lpr; gm.ch = ch; gm.Ppad = 2 * lpr * ch;
+  gm.off_beta = vb >= 0 ? s->vars[vb].offset : -1;
+  gm.beta_buf = dslot >= 0 ? const_cast<double*>(md.pool) + md.derived_off[dslot] : nullptr;
+  gm.beta_seed = dslot >= 0 ? const_cast<double*>(md.pool) + md.derived_off[dslot] + gm.P : nullptr;
+  gm.off_icpt = s->glm_intercept >= 0 ? s->vars[s->glm_intercept].offset : -1;
+  gm.off_sigma = s->glm_sigma >= 0 ? s->vars[s->glm_sigma].offset : -1;
+  gm.tr_sigma = s->glm_sigma >= 0 ? s->vars[s->glm_sigma].transform : NUTS_TR_NONE;
+  gm.sigma_c = s->glm_sigma >= 0 ? 1.0 : (s->glm_family == NUTS_GLM_NORMAL ? s->glm_sigma_const : 1.0);
+  gm.konst = 0.0;
+  for (int64_t i = 0; i < gm.N; ++i) {
+    const double yi = s->glm_y[i];
+    if (s->glm_family == NUTS_GLM_BERNOULLI && !(yi == 0.0 || yi == 1.0)) return refuse("GLM node: Bernoulli observations must be 0 or 1");
+    if (s->glm_family == NUTS_GLM_POISSON) {
+      if (!(yi >= 0.0) || yi != std::floor(yi)) return refuse("GLM node: Poisson observations must be non-negative integers");
+      gm.konst -= std::lgamma(yi + 1.0);     // factln(y): parameter-free (discrete.py:581-597)
+    }
+  }
+  gm.xstride = (gm.P + 1) & ~1; gm.xpad_ = 0;   // 16-byte rows; the layout's last chunks read on into the next row (glm_kernel.h)
+  {   // rows at their own stride + one layout width of zeros behind the last row (what its last chunks read), uploaded in slabs
+    const size_t total = (size_t)gm.N * gm.xstride + (size_t)gm.Ppad;
+    double* xd = m->keep(dev_alloc<double>(total));
+    gm.X = xd;
+    if (xd) {
+      hipMemset(xd + (size_t)gm.N * gm.xstride, 0, (size_t)gm.Ppad * sizeof(double));
+      if (gm.xstride == gm.P) hipMemcpy(xd, s->glm_X, (size_t)gm.N * gm.P * sizeof(double), hipMemcpyHostToDevice);
+      else {
+        const int64_t slab = std::max<int64_t>(1, (int64_t)(1 << 22) / gm.xstride);
+        std::vector<double> buf((size_t)slab * gm.xstride, 0.0);
+        for (int64_t r0 = 0; r0 < gm.N; r0 += slab) {
+          const int64_t nr = std::min<int64_t>(slab, gm.N - r0);
+          for (int64_t r = 0; r < nr; ++r) std::memcpy(&buf[(size_t)r * gm.xstride], s->glm_X + (size_t)(r0 + r) * gm.P, (size_t)gm.P * sizeof(double));
+          hipMemcpy(xd + (size_t)r0 * gm.xstride, buf.data(), (size_t)nr * gm.xstride * sizeof(double), hipMemcpyHostToDevice);
+        }
+      }
+    }
+  }
+  gm.y = m->keep(dev_upload(s->glm_y, (size_t)gm.N));
+  gm.Xt = nullptr;
+  if (gm.P <= GLM_SMALL_P && gm.N <= GLM_SMALL_N) {   // the single-workgroup kernel's copy (small_kernel.h): columns contiguous
+    std::vector<double> xt((size_t)gm.N * gm.P);
+    for (int64_t i = 0; i < gm.N; ++i)
+      for (int p = 0; p < gm.P; ++p) xt[(size_t)p * gm.N + i] = s->glm_X[(size_t)i * gm.P + p];
+    gm.Xt = m->keep(dev_upload(xt.data(), xt.size()));
+  }
+  // grid: every CU gets NUTS_GLM_WG_PER_CU workgroups of four waves (default 4: 16 waves per CU, each with one row-iteration in
+  // flight and one being evaluated).  Measured at configs[3]'s shape on two boxes (profiles/r04h_glm_sweep_workgroups_per_cu.txt,
+  // r04i): 1421 / 1381 / 1380 / 1328 and 1426 / 1387 / 1365 / 1345 leapfrog/s at 4 / 8 / 12 / 16 -- more workgroups shave the
+  // tail of the pass itself but leave more records for k_glm_reduce and a longer launch ramp; the whole leapfrog is fastest at 4
+  // (rocprofv3, same command: 4351 ms of GPU time for 7610 launches at 4 against 5591 ms for 8826 at 12).
+  const int64_t iters = (gm.N + (WAVE / lpr) - 1) / (WAVE / lpr);
+  int64_t nwg = (int64_t)cus * std::max(1, env_int("NUTS_GLM_WG_PER_CU", 4));
+  nwg = std::max<int64_t>(1, std::min<int64_t>(nwg, (iters + 4 * (GLM_BLOCK / WAVE) - 1) / (4 * (GLM_BLOCK / WAVE))));
+  gm.nwg = (int)nwg;
+  gm.part = m->keep(dev_alloc<double>((size_t)gm.nwg * (gm.Ppad + 4)));
+  gm.gdense = m->keep(dev_alloc<double>((size_t)n + 1));
+  gm.lp = gm.gdense ? gm.gdense + n : nullptr;
+  if (gm.part) hipMemset(gm.part, 0, (size_t)gm.nwg * (gm.Ppad + 4) * sizeof(double));
+  if (gm.gdense) hipMemset(gm.gdense, 0, ((size_t)n + 1) * sizeof(double));
+  md.has_glm = 1;
+  m->alg_bytes += 8 * gm.N * (int64_t)gm.P;   // one read of X (SURVEY 8d convention: the node's data once per evaluation)
+  return true;
+}
+
+// Every step sets g_err and returns false on refusal; nuts_model_create destroys the half-built model in ONE place.
+static bool model_build(nuts_model* m, const nuts_model_spec* s) {
+  ModelDev& md = m->md;
+  HIPCHK_FALSE(hipStreamCreateWithFlags(&m->stream, hipStreamNonBlocking));
   m->own_stream = m->stream;
   int n = 0;
   for (int i = 0; i < s->n_vars; ++i) n = std::max(n, s->vars[i].offset + s->vars[i].size);
@@ -1364,8 +1819,8 @@ extern "C" nuts_model* nuts_model_create(const nuts_model_spec* s) {
   md.fdead_mode = 0;
   md.fdead = m->keep(dev_alloc<int32_t>((size_t)std::max(s->n_factors, 1)));
   if (md.fdead) hipMemset(md.fdead, 0, (size_t)std::max(s->n_factors, 1) * sizeof(int32_t));
-  std::vector<VarDev> vars;
-  if (!compile_spec(m, s, vars)) { nuts_model_destroy(m); return nullptr; }
+  CompiledSpec cs;
+  if (!compile_spec(m, s, cs)) return false;
   {   // the spec's data pool, then the engine's own vectors (derived values / seeds), zeroed
     double* pool = m->keep(dev_alloc<double>((size_t)std::max<int64_t>(s->data_pool_len + m->pool_extra, 1)));
     if (pool) {
@@ -1392,7 +1847,7 @@ extern "C" nuts_model* nuts_model_create(const nuts_model_spec* s) {
   m->q_dev = m->keep(dev_alloc<double>(n));
   m->g_dev = m->keep(dev_alloc<double>(n));
   m->lp_dev = m->keep(dev_alloc<double>(2));
-  HIPCHK_NULL(hipHostMalloc((void**)&m->host_pin, (2 * (size_t)n + 2) * sizeof(double), hipHostMallocDefault));
+  HIPCHK_FALSE(hipHostMalloc((void**)&m->host_pin, (2 * (size_t)n + 2) * sizeof(double), hipHostMallocDefault));
   m->alg_bytes = 0;
 
   hipDeviceProp_t prop;
@@ -1400,442 +1855,24 @@ extern "C" nuts_model* nuts_model_create(const nuts_model_spec* s) {
   hipGetDevice(&dev);
   hipGetDeviceProperties(&prop, dev);
   const int cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-
-  if (s->rows_N > 0) {
-    const int D = s->rows_D;
-    if (D < 1 || D > LOGIT_MAXD) { g_err = "logit rows: 1 <= D <= 8 covariates"; nuts_model_destroy(m); return nullptr; }
-    // (D = 2, 4, 8 have every schedule; the other widths run the span-partitioned pass and the group-block pass, one element per
-    // thread in kernel B)
-    const bool d_pow2 = D == 8 || D == 4 || D == 2;
-    if (!d_pow2 && m->ept != 1) { g_err = "logit rows: D must be 2, 4 or 8 for models beyond 65 536 parameters"; nuts_model_destroy(m); return nullptr; }
-    RowsDev& lg = md.lg;
-    md.has_logit = 1;
-    // launch geometry (tunable for experiments; defaults chosen from measurements)
-    m->rows_rpl = 2;
-    m->rows_alternate = env_int("NUTS_ROWS_ALTERNATE", 1) ? 1 : 0;
-    m->rows_occ = 4;
-    // 16 waves per CU are resident at a time (4 per SIMD at 113 VGPRs); two such sets of shorter waves balance the
-    // tail better than one (measured with the folded control: 61.3 us per pass vs 63.0 us at 16, 62.8 at 48, 65.8 at 64)
-    // -- for passes long enough to give every wave a few spans (C2-L: 4.8 per wave); shorter, cache-resident passes are
-    // better off with one set (R = 800 rows per group: 23.5 us at 16 vs 26.2 us at 32)
-    int wpc = env_int("NUTS_ROWS_WAVES_PER_CU", 0);
-    if (wpc <= 0) {
-      const int64_t spans = (s->rows_N + (int64_t)WAVE * m->rows_rpl - 1) / ((int64_t)WAVE * m->rows_rpl);
-      wpc = spans >= (int64_t)cus * 32 * 4 ? 32 : 16;
-    }
-    const int SPAN = WAVE * m->rows_rpl;
-    lg.N = s->rows_N; lg.D = D; lg.G = s->rows_G;
-    lg.Npad = (lg.N + SPAN - 1) / SPAN * SPAN;
-    lg.n_spans = lg.Npad / SPAN;
-    const nuts_var &vmu = s->vars[s->rows_mu], &vsg = s->vars[s->rows_sigma], &vz = s->vars[s->rows_z];
-    if (vmu.size != D || vsg.size != D || vz.size != (int64_t)lg.G * D || vmu.transform != NUTS_TR_NONE ||
-        vz.transform != NUTS_TR_NONE || !(vsg.transform == NUTS_TR_NONE || vsg.transform == NUTS_TR_LOG)) {
-      g_err = "logit rows: mu/sigma/z shapes or transforms unsupported"; nuts_model_destroy(m); return nullptr;
-    }
-    lg.off_mu = vmu.offset; lg.off_sigma = vsg.offset; lg.off_z = vz.offset; lg.sigma_tr = vsg.transform;
-    lg.var_mu = s->rows_mu; lg.var_sigma = s->rows_sigma; lg.var_z = s->rows_z;
-    std::vector<int8_t> yy;
-    std::vector<int64_t> gptr(lg.G + 1, 0);
-    const int32_t* gid = s->rows_gid;
-    for (int64_t i = 0; i < lg.N; ++i) {
-      if (i > 0 && gid[i] < gid[i - 1]) { g_err = "logit rows: group ids must be sorted"; nuts_model_destroy(m); return nullptr; }
-      if (gid[i] < 0 || gid[i] >= lg.G) { g_err = "logit rows: group id out of range"; nuts_model_destroy(m); return nullptr; }
-      gptr[gid[i] + 1] = i + 1;
-    }
-    for (int g = 0; g < lg.G; ++g) gptr[g + 1] = std::max(gptr[g + 1], gptr[g]);  // empty groups
-    lg.gptr = m->keep(dev_upload(gptr.data(), gptr.size()));
-    // ---- group-aligned row pass (rows_ga_kernel.h)?  NUTS_ROWS_GA: 0 never, 1 when the shape suits it (default), 2 whenever
-    // the model structure allows it (tests: ragged / empty / tiny groups through the same kernel) ----
-    {
-      const int want = (s->rows_opts & NUTS_ROWS_NO_GROUP_ALIGNED) ? 0 : env_int("NUTS_ROWS_GA", 1);
-      std::vector<int32_t> tile0(lg.G + 1, 0);
-      int64_t maxT = 0;
-      for (int g = 0; g < lg.G; ++g) {
-        const int64_t T = (gptr[g + 1] - gptr[g] + SPAN - 1) / SPAN;
-        maxT = std::max(maxT, T);
-        tile0[g + 1] = tile0[g] + (int32_t)T;
-      }
-      const int64_t n_tiles = tile0[lg.G];
-      int W = std::min(GA_MAXW, (16 * cus) / std::max(lg.G, 1));   // all G workgroups resident at once (4 waves per SIMD, 16 per CU)
-      if (env_int("NUTS_ROWS_GA_W", 0) > 0) W = std::max(1, std::min(GA_MAXW, env_int("NUTS_ROWS_GA_W", 0)));
-      const double meanT = (double)n_tiles / std::max(lg.G, 1);
-      bool use = false;
-      if (want >= 2) { use = m->ga_struct_ok && m->ept == 1; W = std::max(1, W); }
-      else if (want == 1) use = m->ga_struct_ok && m->ept == 1 && W >= 1 && lg.G >= 2 * cus && meanT >= 4.0 * W && (double)maxT <= 1.5 * meanT + 1.0;
-      // group-BLOCK pass (rows_gb_kernel.h) for small groups: the same closed-form model, a workgroup owns GPW whole groups and
-      // nothing crosses workgroups inside the launch.  NUTS_ROWS_GB=0 keeps such models on the general path (A/B, tests).
-      int gpw = 0;
-      if (!use && want == 1 && !(s->rows_opts & NUTS_ROWS_NO_GROUP_BLOCK) && env_int("NUTS_ROWS_GB", 1) && m->ga_struct_ok && m->ept == 1 &&
-          lg.G >= 64 && maxT <= 16) {
-        gpw = GB_W * (int)((lg.G + GB_W * 512 - 1) / (GB_W * 512));   // a group per wave; more (in sequence) only to stay <= 512 workgroups
-        gpw = std::min(gpw, GB_MAXGPW);
-        if (env_int("NUTS_ROWS_GPW", 0) > 0) gpw = std::max(1, std::min(GB_MAXGPW, env_int("NUTS_ROWS_GPW", 0)));
-        // (slot_sum: at most SLOT_SUM_MAXR records per lane -- block partials + the records of the auxiliary workgroups)
-        const int aux_threads = WAVE * GB_W, auxel = n - lg.G * D;
-        const int naux = m->ga_struct_ok == 2 ? (auxel + aux_threads - 1) / aux_threads : 0;
-        if ((lg.G + gpw - 1) / gpw + naux > WAVE * SLOT_SUM_MAXR) gpw = 0;
-      }
-      if (gpw) { use = true; W = 1; }   // (layout: one chunk per group)
-      if (use && n_tiles * (int64_t)SPAN < ((int64_t)1 << 31) && (gpw || lg.G <= 32 * 8 * GA_MAXCHUNK)) {
-        lg.ga = 1; lg.ga_w = gpw ? GB_W : W;
-        lg.ga_gpw = gpw;
-        lg.ga_bsz = gpw ? gpw : (lg.G + 31) / 32;
-        lg.ga_flags = env_int("NUTS_GA_FLAGS", 0);
-        lg.ga_T_uni = 0; lg.ga_ng_uni = 0;
-        {
-          bool uni = lg.G > 0;
-          for (int g = 1; g < lg.G; ++g) uni = uni && (gptr[g + 1] - gptr[g] == gptr[1] - gptr[0]);
-          if (uni && maxT > 0) { lg.ga_T_uni = (int32_t)maxT; lg.ga_ng_uni = gptr[1] - gptr[0]; }
-        }
-        lg.ga_nblk = (lg.G + lg.ga_bsz - 1) / lg.ga_bsz;
-        // auxiliary workgroups (rows_aux.h): one thread per element that is not a z element
-        lg.ga_auxel = n - lg.G * D;
-        lg.ga_naux = m->ga_struct_ok == 2 ? (lg.ga_auxel + WAVE * lg.ga_w - 1) / (WAVE * lg.ga_w) : 0;
-        lg.ga_nrec = lg.ga_nblk + lg.ga_naux;
-        // chunk (g, w) = the tiles wave w of workgroup g streams, [w T_g / W, (w + 1) T_g / W) -- the split the kernel makes.  Chunks
-        // are placed one after the other with `GA_SKEW` doubles (8448 B = 33 x 256 B) between them, so consecutive chunk starts
-        // differ by an ODD multiple of 256 B modulo any power-of-two channel interleave.
-        // An intercept column (x_{i,0} = 1 for every row, SURVEY 8d's C2) carries no information: it is not stored, the tiles
-        // are [D - 1][SPAN] and the kernel multiplies by the literal 1.0 (rows_ga_kernel.h, GaTileRegs7) -- 57 B per row
-        // instead of 65 on a pass that is bound by the bytes it moves.  NUTS_GA_ONES0=0 keeps the column (A/B, tests).
-        bool ones0 = D == 8 && env_int("NUTS_GA_ONES0", 1) != 0 && lg.N > 0;
-        for (int64_t i = 0; ones0 && i < lg.N; ++i) ones0 = s->rows_X[i * D] == 1.0;
-        const int DX = ones0 ? D - 1 : D;
-        lg.ga_dx = DX;
-        // (the skew between chunks is an ODD multiple of 256 B and a multiple of the tile's column count, so that the y bytes
-        // of a tile sit at its element offset / DX)
-        const int64_t TS = (int64_t)DX * SPAN, GA_SKEW = env_int("NUTS_GA_SKEW", DX == 7 || DX == 5 ? 1120 : 1056);   // 32 x 35, 32 x 33
-        if (GA_SKEW % DX != 0) { g_err = "NUTS_GA_SKEW must be a multiple of the stored column count"; nuts_model_destroy(m); return nullptr; }
-        std::vector<int64_t> coff((size_t)lg.G * W, 0);
-        int64_t pos = 0, max_ct = 0;
-        for (int g = 0; g < lg.G; ++g) {
-          const int64_t T = tile0[g + 1] - tile0[g];
-          for (int w = 0; w < W; ++w) {
-            const int64_t ct = (int64_t)(w + 1) * T / W - (int64_t)w * T / W;
-            coff[(size_t)g * W + w] = pos;
-            pos += ct * TS + GA_SKEW;
-            max_ct = std::max(max_ct, ct);
-          }
-        }
-        lg.ga_cstride_uni = 0;
-        if (lg.ga_T_uni > 0 && lg.ga_T_uni % W == 0) {   // equal chunks: offsets follow from the chunk index
-          lg.ga_cstride_uni = (lg.ga_T_uni / W) * TS + GA_SKEW;
-        } else lg.ga_T_uni = 0;
-        lg.Npad = n_tiles * SPAN; lg.n_spans = n_tiles;
-        // (one tile of slack at the end: a wave without tiles still issues its unconditional first request)
-        std::vector<double> xt((size_t)(pos + TS), 0.0);
-        yy.assign((size_t)(pos / DX + 2 * SPAN), 0);
-        for (int g = 0; g < lg.G; ++g) {
-          const int64_t T = tile0[g + 1] - tile0[g];
-          for (int64_t i = gptr[g]; i < gptr[g + 1]; ++i) {
-            const int64_t r = i - gptr[g], t = r / SPAN, rr = r % SPAN;
-            int w = (int)(((t + 1) * W - 1) / std::max<int64_t>(T, 1));          // the wave whose range [w T / W, (w + 1) T / W) holds tile t
-            while (w > 0 && (int64_t)w * T / W > t) --w;
-            while (w + 1 < W && (int64_t)(w + 1) * T / W <= t) ++w;
-            const int64_t base = coff[(size_t)g * W + w] + (t - (int64_t)w * T / W) * TS;
-            for (int d = D - DX; d < D; ++d) xt[(size_t)(base + (int64_t)(d - (D - DX)) * SPAN + rr)] = s->rows_X[i * D + d];
-            yy[(size_t)(base / DX + rr)] = s->rows_y[i];
-          }
-        }
-        lg.Xt = m->keep(dev_upload(xt.data(), xt.size()));
-        lg.y = m->keep(dev_upload(yy.data(), yy.size()));
-        m->rows_xt_len = (int64_t)xt.size(); m->rows_y_len = (int64_t)yy.size();
-        lg.ga_coff = m->keep(dev_upload(coff.data(), coff.size()));
-        lg.ga_tile0 = m->keep(dev_upload(tile0.data(), tile0.size()));
-        lg.ga_part = m->keep(dev_alloc<double>((size_t)lg.G * PART_STRIDE));
-        // (group-block pass: slot-major, every slot padded to a multiple of 64 records -- the padding stays zero)
-        const size_t bpart_len = gpw ? 2 * (size_t)PART_STRIDE * ((lg.ga_nrec + WAVE - 1) / WAVE * WAVE) : 2 * (size_t)lg.ga_nrec * PART_STRIDE;
-        lg.ga_bpart = m->keep(dev_alloc<double>(bpart_len));
-        lg.ga_ticket = m->keep(dev_alloc<unsigned>(lg.ga_nblk));
-        if (lg.ga_part) hipMemset(lg.ga_part, 0, (size_t)lg.G * PART_STRIDE * sizeof(double));
-        if (lg.ga_bpart) hipMemset(lg.ga_bpart, 0, bpart_len * sizeof(double));
-        if (lg.ga_ticket) hipMemset(lg.ga_ticket, 0, lg.ga_nblk * sizeof(unsigned));
-        m->rows_grid = gpw ? lg.ga_nblk : lg.G;
-      }
-    }
-    if (!lg.ga) {
-    // HBM layout: X in span tiles [n_spans][D][SPAN] (one contiguous block per wave-iteration, each column a
-    // coalesced 16 B/lane load), y int8, group structure as G+1 row pointers (rows are sorted by group)
-    {
-      std::vector<double> xt((size_t)D * lg.Npad, 0.0);
-      for (int64_t i = 0; i < lg.N; ++i) {
-        const int64_t sp = i / SPAN, r = i % SPAN;
-        for (int d = 0; d < D; ++d) xt[((size_t)sp * D + d) * SPAN + r] = s->rows_X[i * D + d];
-      }
-      lg.Xt = m->keep(dev_upload(xt.data(), xt.size()));
-    }
-    yy.assign(lg.Npad, 0);
-    for (int64_t i = 0; i < lg.N; ++i) yy[i] = s->rows_y[i];
-    lg.y = m->keep(dev_upload(yy.data(), yy.size()));
-    const int waves_per_block = ROWS_BLOCK / WAVE;
-    int64_t want_waves = std::min<int64_t>((int64_t)cus * wpc, lg.n_spans);
-    const int nb_main = (int)((want_waves + waves_per_block - 1) / waves_per_block);
-    lg.n_waves = nb_main * waves_per_block;
-    // static tables.  A span that lies entirely inside one group is "uniform" (streamed by the main waves);
-    // the others (group boundary or padding rows inside) are "mixed" and get one wave each.
-    std::vector<int32_t> span_gid(lg.n_spans), mixed_g0, mixed_seg_base, mixed_seg_gid;
-    std::vector<int64_t> mixed_span;
-    for (int64_t sp = 0; sp < lg.n_spans; ++sp) {
-      const int64_t r0 = sp * SPAN, r1 = r0 + SPAN;
-      if (r1 <= lg.N && gid[r0] == gid[r1 - 1]) { span_gid[sp] = gid[r0]; continue; }
-      span_gid[sp] = -1;
-      mixed_span.push_back(sp);
-      mixed_g0.push_back(gid[r0]);
-      mixed_seg_base.push_back((int32_t)mixed_seg_gid.size());
-      int prev = -1;
-      for (int64_t r = r0; r < std::min<int64_t>(r1, lg.N); ++r)
-        if (gid[r] != prev) { prev = gid[r]; mixed_seg_gid.push_back(prev); }
-    }
-    lg.n_mixed = (int32_t)mixed_span.size();
-    lg.n_mixed_seg = (int32_t)mixed_seg_gid.size();
-    std::vector<int32_t> run_ptr(lg.n_waves + 1, 0), seg_gid;
-    std::vector<int4> runs;
-    for (int w = 0; w < lg.n_waves; ++w) {
-      const int64_t s0 = (int64_t)w * lg.n_spans / lg.n_waves, s1 = (int64_t)(w + 1) * lg.n_spans / lg.n_waves;
-      run_ptr[w] = (int32_t)runs.size();
-      for (int64_t sp = s0; sp < s1; ++sp) {
-        if (span_gid[sp] < 0) continue;
-        // runs of the same group inside one wave share a segment even when a mixed span sits between them
-        if (!runs.empty() && (int)runs.size() > run_ptr[w] && runs.back().z == span_gid[sp] && runs.back().x + runs.back().y == sp) {
-          runs.back().y++;
-          continue;
-        }
-        int4 r; r.x = (int)sp; r.y = 1; r.z = span_gid[sp]; r.w = (int)seg_gid.size();
-        runs.push_back(r);
-        seg_gid.push_back(span_gid[sp]);
-      }
-    }
-    run_ptr[lg.n_waves] = (int32_t)runs.size();
-    lg.n_seg = (int32_t)seg_gid.size();
-    auto group_ptr = [&](const std::vector<int32_t>& sg) {
-      std::vector<int32_t> p(lg.G + 1, 0);
-      for (int32_t g : sg) p[g + 1]++;
-      for (int g = 0; g < lg.G; ++g) p[g + 1] += p[g];
-      return p;
-    };
-    // segments are emitted in row order and rows are sorted by group => the segments of a group are contiguous
-    const std::vector<int32_t> gsp = group_ptr(seg_gid), gmp = group_ptr(mixed_seg_gid);
-    // fixed-slot segment layout (model_dev.h) when every group has few main segments and kernel B runs one element per
-    // thread: slot = group * segK + ordinal of the segment inside its group
-    int kmain = 1;
-    for (int g = 0; g < lg.G; ++g) kmain = std::max(kmain, gsp[g + 1] - gsp[g]);
-    lg.segK = 0;
-    if (kmain <= SEG_MAIN_MAX && m->ept == 1 && env_int("NUTS_SEG_FIXED", 1)) {
-      lg.segK = kmain + 2;
-      for (auto& r : runs) r.w = r.z * lg.segK + (r.w - gsp[r.z]);
-    }
-    const size_t seg_doubles = lg.segK ? (size_t)lg.G * lg.segK * D : (size_t)lg.n_seg * D;
-    lg.run_ptr = m->keep(dev_upload(run_ptr.data(), run_ptr.size()));
-    lg.runs = m->keep(dev_upload(runs.data(), runs.size()));
-    lg.gseg_ptr = m->keep(dev_upload(gsp.data(), gsp.size()));
-    lg.seg_part = m->keep(dev_alloc<double>(std::max<size_t>(seg_doubles, 1)));
-    if (lg.seg_part) hipMemset(lg.seg_part, 0, std::max<size_t>(seg_doubles, 1) * sizeof(double));
-    lg.mixed_span = m->keep(dev_upload(mixed_span.data(), mixed_span.size()));
-    lg.mixed_g0 = m->keep(dev_upload(mixed_g0.data(), mixed_g0.size()));
-    lg.mixed_seg_base = m->keep(dev_upload(mixed_seg_base.data(), mixed_seg_base.size()));
-    lg.gmix_ptr = m->keep(dev_upload(gmp.data(), gmp.size()));
-    lg.mixed_part = m->keep(dev_alloc<double>((size_t)lg.n_mixed_seg * D));
-    lg.wave_lp = m->keep(dev_alloc<double>((size_t)lg.n_waves + lg.n_mixed));
-    m->rows_grid = nb_main + (lg.n_mixed + waves_per_block - 1) / waves_per_block;
-    }   // span-partitioned pass
-    m->alg_bytes += lg.N * (8 * (int64_t)D + 1 + 4);  // X row + y + group id per row
-  }
-  if (s->mvn_k > 0) {
-    md.has_mvn = 1;
-    m->explicit_pre = 1;
-    MvnDev& mv = md.mv;
-    mv.k = s->mvn_k; mv.off = s->vars[s->mvn_var].offset;
-    mv.mu = m->keep(dev_upload(s->mvn_mu, mv.k));
-    mv.prec = m->keep(dev_upload(s->mvn_prec, (size_t)mv.k * mv.k));
-    mv.rowq = m->keep(dev_alloc<double>(mv.k));
-    mv.gdense = m->keep(dev_alloc<double>(n));
-    hipMemset(mv.gdense, 0, n * sizeof(double));
-    mv.konst = -0.5 * mv.k * std::log(2.0 * M_PI) - s->mvn_logdet;
-    mv.winv = nullptr; mv.winv_t = nullptr; mv.wy = nullptr;
-    if (s->mvn_winv) {   // "cholesky" solver (include/nuts_mi355.h): W and W^T row-major, so that both mat-vecs read rows
-      const size_t kk = (size_t)mv.k * mv.k;
-      std::vector<double> wt(kk);
-      for (int r = 0; r < mv.k; ++r)
-        for (int cc = 0; cc < mv.k; ++cc) wt[(size_t)cc * mv.k + r] = s->mvn_winv[(size_t)r * mv.k + cc];
-      mv.winv = m->keep(dev_upload(s->mvn_winv, kk));
-      mv.winv_t = m->keep(dev_upload(wt.data(), kk));
-      mv.wy = m->keep(dev_alloc<double>(3 * (size_t)mv.k));
-    }
-    m->mvn_grid = mv.k;   // one workgroup per row
-    m->alg_bytes += 8 * (int64_t)mv.k * mv.k;
-    // the model IS this node (one untransformed vector variable, no other factor): the row-aligned pass finishes the leapfrog
-    // in the mat-vec's own workgroups (kernels.h, k_mvn_aligned)
-    mv.aligned = 0; mv.al_nwg = 0; mv.al_part = nullptr;
-    if (md.lean_ok && !md.has_logit && !mv.winv && mv.off == 0 && mv.k == n && s->n_vars == 1 && s->n_factors == 0 &&
-        s->vars[0].transform == NUTS_TR_NONE && md.n_deferred == 0 && md.n_orphans == 0) {
-      // rows per workgroup; 0: the two-kernel leapfrog.  Fewer, larger workgroups = fewer records for the control work to total and
-      // a cheaper launch: at k = 2048 (C3) 8 rows measured 120 k leapfrog/s against 108 k with 4 and 88 k with 2
-      const int R = env_int("NUTS_MVN_ALIGNED", mv.k >= 1024 ? 8 : 4);
-      if (R == 2 || R == 4 || R == 8 || R == 16) {
-        mv.aligned = R;
-        mv.al_nwg = (mv.k + R - 1) / R;
-        mv.al_part = m->keep(dev_alloc<double>(2 * (size_t)MVA_RS * mv.al_nwg));
-        if (mv.al_part) hipMemset(mv.al_part, 0, 2 * (size_t)MVA_RS * mv.al_nwg * sizeof(double));
-      }
-    }
-  }
-  md.has_mix = 0;
-  if (s->mix_N > 0) {
-    MixDev& mx = md.mix;
-    auto bad = [&](const char* msg) { g_err = msg; nuts_model_destroy(m); return (nuts_model*)nullptr; };
-    if (s->rows_N > 0 || s->mvn_k > 0) return bad("mixture node: not together with another dense node");
-    if (s->mix_K < 1 || s->mix_K > MIX_MAXK) return bad("mixture node: 1 <= K <= 16 components");
-    if (!s->mix_y) return bad("mixture node: no observations");
-    auto var_ok = [&](int v) { return v >= 0 && v < s->n_vars && s->vars[v].size == s->mix_K && !vars[v].deferred; };
-    if (!var_ok(s->mix_mu)) return bad("mixture node: mu must be a variable with K elements (not a scalar that broadcasts into another factor)");
-    if (s->mix_sigma >= 0 && (!var_ok(s->mix_sigma) || (s->vars[s->mix_sigma].transform != NUTS_TR_NONE && s->vars[s->mix_sigma].transform != NUTS_TR_LOG)))
-      return bad("mixture node: sigma must be a variable with K elements, untransformed or log-transformed");
-    if (s->mix_sigma < 0 && !s->mix_sigma_const) return bad("mixture node: sigma is neither a variable nor a constant");
-    if (s->mix_w_simplex) {
-      const int v = s->mix_w_logits;
-      if (s->mix_K < 3 || v < 0 || v >= s->n_vars || s->vars[v].size != s->mix_K - 1 || vars[v].deferred || s->vars[v].transform != NUTS_TR_NONE || !s->mix_w_alpha)
-        return bad("mixture node: Dirichlet weights are a variable of K - 1 elements (the simplex-transformed value, K >= 3) with K concentrations");
-      for (int k = 0; k < s->mix_K; ++k)
-        if (!(s->mix_w_alpha[k] > 0)) return bad("mixture node: Dirichlet concentrations a > 0");   // multivariate.py Dirichlet.logp check_parameters
-    } else
-    if (s->mix_w_logits >= 0 && (!var_ok(s->mix_w_logits) || s->vars[s->mix_w_logits].transform != NUTS_TR_NONE))
-      return bad("mixture node: the weight logits must be an untransformed variable with K elements");
-    if (s->mix_w_logits < 0 && !s->mix_w_const) return bad("mixture node: the weights are neither softmax(logits) nor constants");
-    if (s->vars[s->mix_mu].transform != NUTS_TR_NONE) return bad("mixture node: mu must be untransformed");
-    if (s->mix_assign >= s->n_data || (s->mix_assign >= 0 && s->data[s->mix_assign].size != s->mix_N))
-      return bad("mixture node: one assignment per observed row");
-    mx.N = s->mix_N; mx.K = s->mix_K;
-    mx.off_mu = s->vars[s->mix_mu].offset;
-    mx.off_sigma = s->mix_sigma >= 0 ? s->vars[s->mix_sigma].offset : -1;
-    mx.tr_sigma = s->mix_sigma >= 0 ? s->vars[s->mix_sigma].transform : NUTS_TR_NONE;
-    mx.off_w = s->mix_w_logits >= 0 ? s->vars[s->mix_w_logits].offset : -1;
-    for (int k = 0; k < MIX_MAXK; ++k) { mx.sigma_c[k] = 1.0; mx.logw_c[k] = 0.0; mx.alpha[k] = 1.0; }
-    mx.w_simplex = s->mix_w_simplex ? 1 : 0; mx.pad_ = 0; mx.w_konst = 0.0;
-    if (mx.w_simplex) {
-      double sa = 0.0, sl = 0.0;
-      for (int k = 0; k < mx.K; ++k) { mx.alpha[k] = s->mix_w_alpha[k]; sa += mx.alpha[k]; sl += std::lgamma(mx.alpha[k]); }
-      mx.w_konst = std::lgamma(sa) - sl + std::log((double)mx.K);
-    }
-    if (s->mix_sigma < 0)
-      for (int k = 0; k < mx.K; ++k) {
-        if (!(s->mix_sigma_const[k] > 0)) return bad("mixture node: sigma > 0");   // continuous.py:532 check_parameters
-        mx.sigma_c[k] = s->mix_sigma_const[k];
-      }
-    if (s->mix_w_logits < 0) {
-      double sum = 0.0;
-      for (int k = 0; k < mx.K; ++k) { if (!(s->mix_w_const[k] >= 0 && s->mix_w_const[k] <= 1)) return bad("mixture node: 0 <= weights <= 1, sum(weights) == 1"); sum += s->mix_w_const[k]; }
-      if (std::fabs(sum - 1.0) > 1e-8) return bad("mixture node: 0 <= weights <= 1, sum(weights) == 1");   // mixture.py:487-493
-      for (int k = 0; k < mx.K; ++k) mx.logw_c[k] = std::log(s->mix_w_const[k]);
-    }
-    mx.y = m->keep(dev_upload(s->mix_y, (size_t)s->mix_N));
-    mx.assign = s->mix_assign >= 0 ? md.pool + s->data[s->mix_assign].offset : nullptr;
-    mx.nwg = (int)std::max<int64_t>(1, std::min<int64_t>(512, (s->mix_N + 4 * MIX_BLOCK - 1) / (4 * MIX_BLOCK)));
-    mx.part = m->keep(dev_alloc<double>((size_t)mx.nwg * (3 * MIX_MAXK + 1)));
-    mx.gdense = m->keep(dev_alloc<double>((size_t)n + 1));
-    mx.lp = mx.gdense + n;
-    if (mx.part) hipMemset(mx.part, 0, (size_t)mx.nwg * (3 * MIX_MAXK + 1) * sizeof(double));
-    if (mx.gdense) hipMemset(mx.gdense, 0, ((size_t)n + 1) * sizeof(double));
-    md.has_mix = 1;
-    m->alg_bytes += 8 * s->mix_N + (s->mix_assign >= 0 ? 8 * s->mix_N : 0);
-  }
-  md.has_glm = 0;
-  if (s->glm_N > 0) {
-    GlmDev& gm = md.glm;
-    auto bad = [&](const char* msg) { g_err = msg; nuts_model_destroy(m); return (nuts_model*)nullptr; };
-    if (s->rows_N > 0 || s->mix_N > 0) return bad("GLM node: together with an MvNormal node only, not with the logit rows or the mixture node");
-    if (s->mvn_k > 0 && s->mvn_winv) return bad("GLM node next to an MvNormal node: the MvNormal node's precision solver only");
-    if (s->glm_P < 1 || s->glm_P > NUTS_GLM_MAXP) return bad("GLM node: 1 <= P <= 512 covariates");
-    if (!s->glm_X || !s->glm_y) return bad("GLM node: no design matrix / observations");
-    if (s->glm_family < NUTS_GLM_NORMAL || s->glm_family > NUTS_GLM_POISSON) return bad("GLM node: unknown family");
-    const int vb = s->glm_beta;
-    int dslot = -1;   // beta a derived vector: its place in the model's list of derived vectors
-    if (vb < 0) {
-      for (int t = 0; t < md.n_derived; ++t) if (md.derived_f[t] == s->glm_beta_derived) dslot = t;
-      if (dslot < 0 || s->factors[s->glm_beta_derived].size != s->glm_P) return bad("GLM node: glm_beta_derived must name a NUTS_D_DERIVED factor of P elements");
-    } else if (vb >= s->n_vars || s->vars[vb].size != s->glm_P || s->vars[vb].transform != NUTS_TR_NONE)
-      return bad("GLM node: beta must be an untransformed variable with P elements (or a derived vector)");
-    auto scalar_ok = [&](int v, bool log_ok) {
-      return v >= 0 && v < s->n_vars && s->vars[v].size == 1 && (s->vars[v].transform == NUTS_TR_NONE || (log_ok && s->vars[v].transform == NUTS_TR_LOG));
-    };
-    if (s->glm_intercept >= 0 && !scalar_ok(s->glm_intercept, false)) return bad("GLM node: the intercept must be an untransformed scalar variable");
-    if (s->glm_family == NUTS_GLM_NORMAL) {
-      if (s->glm_sigma >= 0 && !scalar_ok(s->glm_sigma, true)) return bad("GLM node: sigma must be a scalar variable, untransformed or log-transformed");
-      if (s->glm_sigma < 0 && !(s->glm_sigma_const > 0)) return bad("GLM node: sigma > 0");   // continuous.py:532 check_parameters
-    } else if (s->glm_sigma >= 0) return bad("GLM node: only the Normal family has a sigma");
-    gm.N = s->glm_N; gm.P = s->glm_P; gm.family = s->glm_family;
-    // register layout: a row in the lanes of a group of `lpr`, `ch` 16-byte chunks per lane (glm_kernel.h)
-    int lpr = 1;
-    while (8 * lpr < gm.P) lpr *= 2;
-    int ch = (gm.P + 2 * lpr - 1) / (2 * lpr);
-    if (lpr == 1) ch = ch == 3 ? 4 : ch;       // instantiated: 1, 2, 4
-    else if (lpr < 32) ch = 4;                 // 4 only
-    else ch = std::max(ch, 3);                 // 3 or 4
-    gm.lpr = lpr; gm.ch = ch; gm.Ppad = 2 * lpr * ch;
-    gm.off_beta = vb >= 0 ? s->vars[vb].offset : -1;
-    gm.beta_buf = dslot >= 0 ? const_cast<double*>(md.pool) + md.derived_off[dslot] : nullptr;
-    gm.beta_seed = dslot >= 0 ? const_cast<double*>(md.pool) + md.derived_off[dslot] + gm.P : nullptr;
-    gm.off_icpt = s->glm_intercept >= 0 ? s->vars[s->glm_intercept].offset : -1;
-    gm.off_sigma = s->glm_sigma >= 0 ? s->vars[s->glm_sigma].offset : -1;
-    gm.tr_sigma = s->glm_sigma >= 0 ? s->vars[s->glm_sigma].transform : NUTS_TR_NONE;
-    gm.sigma_c = s->glm_sigma >= 0 ? 1.0 : (s->glm_family == NUTS_GLM_NORMAL ? s->glm_sigma_const : 1.0);
-    gm.konst = 0.0;
-    for (int64_t i = 0; i < gm.N; ++i) {
-      const double yi = s->glm_y[i];
-      if (s->glm_family == NUTS_GLM_BERNOULLI && !(yi == 0.0 || yi == 1.0)) return bad("GLM node: Bernoulli observations must be 0 or 1");
-      if (s->glm_family == NUTS_GLM_POISSON) {
-        if (!(yi >= 0.0) || yi != std::floor(yi)) return bad("GLM node: Poisson observations must be non-negative integers");
-        gm.konst -= std::lgamma(yi + 1.0);     // factln(y): parameter-free (discrete.py:581-597)
-      }
-    }
-    gm.xstride = (gm.P + 1) & ~1; gm.xpad_ = 0;   // 16-byte rows; the layout's last chunks read on into the next row (glm_kernel.h)
-    {   // rows at their own stride + one layout width of zeros behind the last row (what its last chunks read), uploaded in slabs
-      const size_t total = (size_t)gm.N * gm.xstride + (size_t)gm.Ppad;
-      double* xd = m->keep(dev_alloc<double>(total));
-      gm.X = xd;
-      if (xd) {
-        hipMemset(xd + (size_t)gm.N * gm.xstride, 0, (size_t)gm.Ppad * sizeof(double));
-        if (gm.xstride == gm.P) hipMemcpy(xd, s->glm_X, (size_t)gm.N * gm.P * sizeof(double), hipMemcpyHostToDevice);
-        else {
-          const int64_t slab = std::max<int64_t>(1, (int64_t)(1 << 22) / gm.xstride);
-          std::vector<double> buf((size_t)slab * gm.xstride, 0.0);
-          for (int64_t r0 = 0; r0 < gm.N; r0 += slab) {
-            const int64_t nr = std::min<int64_t>(slab, gm.N - r0);
-            for (int64_t r = 0; r < nr; ++r) std::memcpy(&buf[(size_t)r * gm.xstride], s->glm_X + (size_t)(r0 + r) * gm.P, (size_t)gm.P * sizeof(double));
-            hipMemcpy(xd + (size_t)r0 * gm.xstride, buf.data(), (size_t)nr * gm.xstride * sizeof(double), hipMemcpyHostToDevice);
-          }
-        }
-      }
-    }
-    gm.y = m->keep(dev_upload(s->glm_y, (size_t)gm.N));
-    gm.Xt = nullptr;
-    if (gm.P <= GLM_SMALL_P && gm.N <= GLM_SMALL_N) {   // the single-workgroup kernel's copy (small_kernel.h): columns contiguous
-      std::vector<double> xt((size_t)gm.N * gm.P);
-      for (int64_t i = 0; i < gm.N; ++i)
-        for (int p = 0; p < gm.P; ++p) xt[(size_t)p * gm.N + i] = s->glm_X[(size_t)i * gm.P + p];
-      gm.Xt = m->keep(dev_upload(xt.data(), xt.size()));
-    }
-    // grid: every CU gets NUTS_GLM_WG_PER_CU workgroups of four waves (default 4: 16 waves per CU, each with one row-iteration in
-    // flight and one being evaluated).  Measured at configs[3]'s shape on two boxes (profiles/r04h_glm_sweep_workgroups_per_cu.txt,
-    // r04i): 1421 / 1381 / 1380 / 1328 and 1426 / 1387 / 1365 / 1345 leapfrog/s at 4 / 8 / 12 / 16 -- more workgroups shave the
-    // tail of the pass itself but leave more records for k_glm_reduce and a longer launch ramp; the whole leapfrog is fastest at 4
-    // (rocprofv3, same command: 4351 ms of GPU time for 7610 launches at 4 against 5591 ms for 8826 at 12).
-    const int64_t iters = (gm.N + (WAVE / lpr) - 1) / (WAVE / lpr);
-    int64_t nwg = (int64_t)cus * std::max(1, env_int("NUTS_GLM_WG_PER_CU", 4));
-    nwg = std::max<int64_t>(1, std::min<int64_t>(nwg, (iters + 4 * (GLM_BLOCK / WAVE) - 1) / (4 * (GLM_BLOCK / WAVE))));
-    gm.nwg = (int)nwg;
-    gm.part = m->keep(dev_alloc<double>((size_t)gm.nwg * (gm.Ppad + 4)));
-    gm.gdense = m->keep(dev_alloc<double>((size_t)n + 1));
-    gm.lp = gm.gdense ? gm.gdense + n : nullptr;
-    if (gm.part) hipMemset(gm.part, 0, (size_t)gm.nwg * (gm.Ppad + 4) * sizeof(double));
-    if (gm.gdense) hipMemset(gm.gdense, 0, ((size_t)n + 1) * sizeof(double));
-    md.has_glm = 1;
-    m->alg_bytes += 8 * gm.N * (int64_t)gm.P;   // one read of X (SURVEY 8d convention: the node's data once per evaluation)
-  }
-  if (!build_lins(m, s, vars)) { nuts_model_destroy(m); return nullptr; }
-  if (!build_sweep_fast(m, s, vars)) { nuts_model_destroy(m); return nullptr; }
+  if (!build_rows(m, s, cus) || !build_mvn(m, s) || !build_mix(m, s, cs) || !build_glm(m, s, cs, cus) || !build_lins(m, s, cs) ||
+      !build_sweep_fast(m, s, cs))
+    return false;
   for (void* p : m->owned)
-    if (!p) { g_err = "device allocation failed"; nuts_model_destroy(m); return nullptr; }
-  HIPCHK_NULL(hipDeviceSynchronize());
+    if (!p) return refuse("device allocation failed");
+  HIPCHK_FALSE(hipDeviceSynchronize());
+  return true;
+}
+
+extern "C" nuts_model* nuts_model_create(const nuts_model_spec* s) {
+  if (!s || s->n_vars <= 0) { g_err = "empty model spec"; return nullptr; }
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) {
+    g_err = "no HIP device visible: libnuts_mi355 requires an MI355X (gfx950); there is no CPU fallback";
+    return nullptr;
+  }
+  auto* m = new nuts_model();
+  if (!model_build(m, s)) { nuts_model_destroy(m); return nullptr; }
   return m;
 }
 
