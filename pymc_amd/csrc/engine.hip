@@ -2657,9 +2657,6 @@ static int potential_update(nuts_chain* c, const double* x_dev, const double* g_
   return NUTS_OK;
 }
 
-// Upload (q0, normals|p, uniforms), evaluate the model at q0 (plain A/B/C) and initialise the trajectory.
-//   p_exact: the second vector is the momentum itself (integrator tests) instead of standard normals
-//   dir_forced: +1/-1 fixes the direction (HMC / integrator tests); 0 = draw it from uniforms[0] (nuts.py:215)
 #define LOGS_FIRST 80   // doublings 0..5 consume uniform indices < 2^6 + 6 = 70
 
 // make sure the logarithms of uniforms [0, upto) are on the device before the launches that may read them are queued
@@ -2725,6 +2722,139 @@ static int host_pot_error(nuts_chain* c) {
   return rc;
 }
 
+// ---- steps every draw entry point shares (nuts_chain_draw, draw_many_general, nuts_chain_draw_many, nuts_chain_draw_hmc) ----
+using clk = std::chrono::steady_clock;
+static inline double secs(clk::time_point a, clk::time_point b) { return std::chrono::duration<double>(b - a).count(); }
+
+// wall and CPU clock of a transition, for its statistics record (perf_counter_start, perf_counter_diff, process_time_diff)
+struct DrawClock {
+  clk::time_point t0 = clk::now();
+  std::clock_t c0 = std::clock();
+  double perf_start() const { return std::chrono::duration<double>(t0.time_since_epoch()).count(); }
+  double wall() const { return secs(t0, clk::now()); }
+  double cpu() const { return (double)(std::clock() - c0) / CLOCKS_PER_SEC; }
+};
+
+// what the coming transition runs with (base_hmc.py:226-228 ; nuts.py:205-208); the step size is also left in c->step_size
+struct DrawPlan {
+  bool adapt;
+  double step_size;
+  int max_depth, need_uni;   // need_uni: uniforms of the worst-case tree
+};
+static DrawPlan plan_draw(nuts_chain* c) {
+  DrawPlan p{};
+  p.adapt = c->tune && c->cfg.adapt_step_size;
+  p.step_size = c->step_size = c->da.current(p.adapt);
+  p.max_depth = (c->tune && c->iter_count < 200) ? c->cfg.early_max_treedepth : c->cfg.max_treedepth;
+  p.need_uni = (1 << p.max_depth) + p.max_depth + 1;
+  return p;
+}
+
+// the usual case inside a chain: q0 is bit for bit the proposal this chain returned last time, whose gradient and
+// logp are still on the device -- the model pass at q0 would reproduce exactly those numbers.  The cache is spent either way.
+static bool start_cached(nuts_chain* c, const double* q0) {
+  const bool cached = c->cache_ok && c->cache_epoch == c->m->data_epoch && std::memcmp(q0, c->last_q.data(), c->n * sizeof(double)) == 0;
+  c->cache_ok = false;
+  return cached;
+}
+// ... and the proposal just returned (its position on the host, its (q, grad) still on the device) becomes the next one's
+static void commit_start_cache(nuts_chain* c, const double* q_host, double logp) {
+  c->last_q.assign(q_host, q_host + c->n);
+  c->last_logp = logp; c->cache_ok = true; c->cache_epoch = c->m->data_epoch;
+}
+
+// base_hmc.py:205-224: SamplingError("Bad initial energy"), after potential.raise_ok
+static int bad_initial_energy(nuts_chain* c) {
+  if (check_mass_matrix(c) == NUTS_OK) g_err = "Bad initial energy, check any log probabilities that are inf or -inf, nan or very small";
+  return NUTS_E_BAD_ENERGY;
+}
+
+// keep the leaf the integrator started from and the one it diverged to (base_hmc.py:249-258); both are still in the arena
+static int read_divergence_points(nuts_chain* c, int div_t) {
+  const int n = c->n;
+  const ArenaDev& A = c->A;
+  const int dir = div_t > 0 ? 1 : -1;   // a leaf's index is its parent's + sign(eps) and the start state is 0
+  c->div_source.resize(n); c->div_dest.resize(n);
+  HIPCHK(hipMemcpy(c->div_dest.data(), A.Q + (int64_t)(div_t & (A.S - 1)) * n, n * sizeof(double), hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(c->div_source.data(), A.Q + (int64_t)((div_t - dir) & (A.S - 1)) * n, n * sizeof(double), hipMemcpyDeviceToHost));
+  return NUTS_OK;
+}
+
+// the statistics record of a transition from its device record and the chain's scalars (after adaptation and the counters)
+static void fill_draw_stats(const nuts_chain* c, const DrawOut& o, bool exhausted, int64_t evals, double perf_start, double wall, double cpu,
+                            nuts_draw_stats* stats) {
+  const bool diverging = o.diverging != 0;
+  std::memset(stats, 0, sizeof(*stats));
+  stats->depth = o.depth;
+  stats->step_size = std::exp(c->da.log_step);
+  stats->step_size_bar = std::exp(c->da.log_bar);
+  stats->mean_tree_accept = std::exp(o.log_accept_sum) / o.n_proposals;
+  stats->tree_size = o.n_proposals;
+  stats->diverging = diverging;
+  stats->reached_max_treedepth = (exhausted && !c->tune) ? 1 : 0;  // nuts.py:220-221
+  stats->divergences = c->divergences;
+  stats->energy_error = o.energy - o.E0;
+  stats->energy = o.energy;
+  stats->max_energy_error = o.max_energy_change;
+  stats->model_logp = o.logp;
+  stats->index_in_trajectory = o.proposal;
+  stats->n_uniforms_consumed = o.cursor;
+  stats->warning = diverging ? 1 : 0;
+  stats->divergence_energy_change = o.div_dE;
+  stats->n_model_evals = evals;
+  stats->perf_counter_start = perf_start;
+  stats->perf_counter_diff = wall;
+  stats->process_time_diff = cpu;
+}
+
+// staging of the multi-draw calls, grown on demand: `in_doubles` doubles going in, `out_bytes` coming back
+static int ensure_many_staging(nuts_chain* c, size_t in_doubles, size_t out_bytes) {
+  if (in_doubles <= c->many_in_cap && out_bytes <= c->many_out_cap) return NUTS_OK;
+  HIPCHK(hipStreamSynchronize(c->m->stream));
+  if (c->many_in_host) hipHostFree(c->many_in_host);
+  if (c->many_out_host) hipHostFree(c->many_out_host);
+  if (c->many_in_dev) hipFree(c->many_in_dev);
+  if (c->many_out_dev) hipFree(c->many_out_dev);
+  c->many_in_host = nullptr; c->many_out_host = nullptr; c->many_in_dev = nullptr; c->many_out_dev = nullptr;
+  c->many_in_cap = c->many_out_cap = 0;
+  HIPCHK(hipHostMalloc((void**)&c->many_in_host, in_doubles * sizeof(double), hipHostMallocDefault));
+  HIPCHK(hipHostMalloc((void**)&c->many_out_host, out_bytes, hipHostMallocDefault));
+  HIPCHK(hipMalloc((void**)&c->many_in_dev, in_doubles * sizeof(double)));
+  HIPCHK(hipMalloc((void**)&c->many_out_dev, out_bytes));
+  c->many_in_cap = in_doubles; c->many_out_cap = out_bytes;
+  return NUTS_OK;
+}
+
+// Initialise the trajectory of a transition whose start state is in slot 0 of the arena or, `from_prev`, is the previous
+// proposal ((q, grad) in out_dev; logp in `prev_record` on the device when given, else c->last_logp).
+//   normals_dev: standard normals for the momentum, on the device
+//   p_exact: that vector is the momentum itself (integrator tests, host potentials) instead of standard normals
+//   dir_forced: +1/-1 fixes the direction (HMC / integrator tests); 0 = draw it from uniforms[0] (nuts.py:215)
+// A host potential's failure is parked in c->cb_err and nothing more is queued (dense_velocity).
+static int enqueue_draw_start(nuts_chain* c, const double* normals_dev, bool p_exact, bool from_prev, double step_size, int dir_forced,
+                              int max_depth, const DrawOut* prev_record) {
+  const int n = c->n;
+  hipStream_t s = c->m->stream;
+  ArenaDev& A = c->A;
+  if (c->dense) {
+    // p0 = W z (or the given momentum), v0 = C p0   (quadpotential.py:704-711)
+    if (p_exact) HIPCHK(hipMemcpyAsync(A.P, normals_dev, n * sizeof(double), hipMemcpyDeviceToDevice, s));
+    else if (c->full_adapt) fa_random(c, normals_dev, A.P);
+    else hipLaunchKernelGGL(k_dense_mv, dim3(c->mv_grid), dim3(256), 0, s, c->dense_W, normals_dev, A.P, n, (const double*)nullptr,
+                            (double*)nullptr, 0.0, (const int*)nullptr);
+    dense_velocity(c, A.P, A.V, nullptr, nullptr, 0.0, nullptr, VEL_START);
+    if (c->cb_err) return NUTS_OK;
+  }
+  hipLaunchKernelGGL(k_draw_start, dim3(A.nblk), dim3(VEC_THREADS), 0, s, A, normals_dev, p_exact ? normals_dev : (const double*)nullptr,
+                     c->kin_part, from_prev ? (const double*)c->out_dev : (const double*)nullptr,
+                     from_prev ? (const double*)(c->out_dev + n) : (const double*)nullptr, c->dense);
+  hipLaunchKernelGGL(k_draw_ctl_start, dim3(1), dim3(64), 0, s, A, c->kin_part, step_size, dir_forced, max_depth, c->st_dev,
+                     from_prev ? 1 : 0, c->last_logp, prev_record);
+  return NUTS_OK;
+}
+
+// Upload (q0, normals|p, uniforms), evaluate the model at q0 (plain A/B/C) unless `allow_cache` and q0 is the cached start
+// state, and initialise the trajectory (p_exact, dir_forced: enqueue_draw_start).
 static int draw_begin(nuts_chain* c, const double* q0, const double* normals, const double* uniforms, int n_uniforms,
                       double step_size, int max_depth, bool p_exact, int dir_forced, bool allow_cache = false) {
   const int n = c->n;
@@ -2732,10 +2862,7 @@ static int draw_begin(nuts_chain* c, const double* q0, const double* normals, co
     if (!c->hp_velocity) { g_err = "NUTS_POT_HOST chain: nuts_chain_set_host_potential has not been called"; return NUTS_E_ARG; }
     p_exact = true;   // `normals` IS potential.random()
   }
-  // the usual case inside a chain: q0 is bit for bit the proposal this chain returned last time, whose gradient and
-  // logp are still on the device -- the model pass at q0 would reproduce exactly those numbers
-  const bool cached = allow_cache && c->cache_ok && c->cache_epoch == c->m->data_epoch && std::memcmp(q0, c->last_q.data(), n * sizeof(double)) == 0;
-  c->cache_ok = false;
+  const bool cached = start_cached(c, q0) && allow_cache;
   hipStream_t s = c->m->stream;
   ArenaDev& A = c->A;
   const int nu = std::min(n_uniforms, c->n_uni_cap);
@@ -2760,50 +2887,40 @@ static int draw_begin(nuts_chain* c, const double* q0, const double* normals, co
     HIPCHK(hipMemcpyAsync(A.Q, c->stage_dev, n * sizeof(double), hipMemcpyDeviceToDevice, s));
     model_enqueue_plain(c->m, A.Q, A.G, A.LOGP);
   }
-  if (c->dense) {
-    // p0 = W z (or the given momentum), v0 = C p0   (quadpotential.py:704-711)
-    if (p_exact) HIPCHK(hipMemcpyAsync(A.P, c->stage_dev + n, n * sizeof(double), hipMemcpyDeviceToDevice, s));
-    else if (c->full_adapt) fa_random(c, c->stage_dev + n, A.P);
-    else hipLaunchKernelGGL(k_dense_mv, dim3(c->mv_grid), dim3(256), 0, s, c->dense_W, c->stage_dev + n, A.P, n, (const double*)nullptr,
-                            (double*)nullptr, 0.0, (const int*)nullptr);
-    dense_velocity(c, A.P, A.V, nullptr, nullptr, 0.0, nullptr, VEL_START);
-    if (c->cb_err) return host_pot_error(c);
-  }
-  hipLaunchKernelGGL(k_draw_start, dim3(A.nblk), dim3(VEC_THREADS), 0, s, A, c->stage_dev + n,
-                     p_exact ? (const double*)(c->stage_dev + n) : (const double*)nullptr, c->kin_part,
-                     cached ? (const double*)c->out_dev : (const double*)nullptr, cached ? (const double*)(c->out_dev + n) : (const double*)nullptr,
-                     c->dense);
-  hipLaunchKernelGGL(k_draw_ctl_start, dim3(1), dim3(64), 0, s, A, c->kin_part, step_size, dir_forced, max_depth, c->st_dev,
-                     cached ? 1 : 0, c->last_logp, (const DrawOut*)nullptr);
+  const int rc = enqueue_draw_start(c, c->stage_dev + n, p_exact, cached, step_size, dir_forced, max_depth, nullptr);
+  if (rc) return rc;
+  if (c->cb_err) return host_pot_error(c);
   return NUTS_OK;
 }
 
-static int sync_status(nuts_chain* c) {   // the status record is host memory: a stream sync makes it current
-  HIPCHK(hipStreamSynchronize(c->m->stream));
-  return NUTS_OK;
-}
-
-// Wait until the control kernel of the last leaf of a doubling has published sequence number `seq`
-// (spin on the mapped record; falls back to an error after 60 s so that a lost kernel cannot hang the process).
-static int wait_status(nuts_chain* c, int seq, unsigned* flags, int* cursor = nullptr) {
-  volatile unsigned long long* word = &c->st_host->word[seq & (ST_SLOTS - 1)];
-  const auto t0 = std::chrono::steady_clock::now();
+// Spin until the 32-bit sequence number at bit `shift` of a mapped word the device publishes equals `seq`; the word as seen
+// then goes to `*seen`.  Falls back to an error after 60 s so that a lost kernel cannot hang the process; `unpublished`:
+// the message when the stream ran dry and the word never came.
+static int wait_seq(nuts_chain* c, const volatile unsigned long long* word, int shift, unsigned seq, const char* unpublished,
+                    unsigned long long* seen) {
+  const auto t0 = clk::now();
   unsigned long long w;
+  for (unsigned spins = 0; (unsigned)((w = *word) >> shift) != seq; ++spins) {
+    if ((spins & 0xfffff) == 0xfffff) {
+      if (hipStreamQuery(c->m->stream) == hipSuccess && (unsigned)(*word >> shift) != seq) { g_err = unpublished; return NUTS_E_HIP; }
+      if (clk::now() - t0 > std::chrono::seconds(60)) { g_err = "timed out waiting for the device"; return NUTS_E_HIP; }
+    }
+  }
+  std::atomic_thread_fence(std::memory_order_acquire);
+  *seen = w;
+  return NUTS_OK;
+}
+
+// Wait until the control kernel of the last leaf of a doubling has published sequence number `seq`.
+static int wait_status(nuts_chain* c, int seq, unsigned* flags, int* cursor = nullptr) {
   // (member of a chain group: the chain stays a lockstep partner while it waits -- everything this status depends on has been
   // submitted, since a deposit returns only after its launch was; partners that are ahead wait at their next deposit until this
   // chain has seen its status and deposits too, which keeps the chains of a group leaf by leaf in the same launches.  Letting
   // the others go on instead was measured: the host runs far ahead of the device, every chain spends most of its time here, and
   // the chains took turns -- 1.17 chains per launch.)
-  for (unsigned spins = 0; (unsigned)((w = *word) >> 32) != (unsigned)seq; ++spins) {
-    if ((spins & 0xfffff) == 0xfffff) {
-      if (hipStreamQuery(c->m->stream) == hipSuccess && (unsigned)(*word >> 32) != (unsigned)seq) {
-        g_err = "control kernel finished without publishing its status";
-        return NUTS_E_HIP;
-      }
-      if (std::chrono::steady_clock::now() - t0 > std::chrono::seconds(60)) { g_err = "timed out waiting for the device"; return NUTS_E_HIP; }
-    }
-  }
-  std::atomic_thread_fence(std::memory_order_acquire);
+  unsigned long long w = 0;
+  const int rc = wait_seq(c, &c->st_host->word[seq & (ST_SLOTS - 1)], 32, (unsigned)seq, "control kernel finished without publishing its status", &w);
+  if (rc) return rc;
   *flags = (unsigned)w & 0xffu;
   if (cursor) *cursor = (int)(((unsigned)w >> 8) & 0xffffffu);
   return NUTS_OK;
@@ -2832,28 +2949,35 @@ static inline void enqueue_leaf(nuts_chain* c, const Geometry& gm, int j, int d,
   io.lean = m->md.lean_ok && !c->dense && (!io.explicit_pre || m->md.n_deferred == 0);
   const bool foldable = c->fold_ctl && (mode == MODE_TREE || (mode == MODE_SIMPLE && n_simple > 0));
   const bool last = mode == MODE_TREE ? j + 1 == (1 << d) : j + 1 == n_simple;
-  if (io.lean && io.explicit_pre && foldable) {
-    // MvNormal model on the lean path: kernel B of leaf j also materialises the first half of leaf j+1, the control
-    // work of leaf j-1 rides in workgroup 0 of this leaf's mat-vec; the last leaf gets a control launch of its own
-    const bool al_xpre = m->md.mv.aligned && mode == MODE_TREE && c->xpre;
-    if (j == 0 && !(al_xpre && c->pre_done)) hipLaunchKernelGGL(k_leaf_pre, dim3(A.nblk), dim3(VEC_THREADS), 0, s, A, io, j);
-    if (j == 0) c->pre_done = false;
-    io.pre_next = last ? 0 : 1;
-    if (last && al_xpre && c->defer_last_ctl && c->next_dir != 0) {
-      // the next doubling is queued right behind this leaf: same side -> its first leaf starts from this one (what pre_next = 1
-      // writes); other side -> from the tree's other edge state (pre_next = 3: k_leaf_pre's arithmetic on this workgroup's rows)
-      io.pre_next = c->next_dir == gm.dir ? 1 : 3;
-      c->pre_done = true;
+  if (io.lean && foldable) {
+    // folded control (kernels.h): the control work of leaf j-1 rides in workgroup 0 of this leaf's data pass (the MvNormal
+    // mat-vec, the row pass); only the last leaf of the doubling (of the fixed-length trajectory) -- whose result the host
+    // waits for -- gets a control launch of its own
+    if (io.explicit_pre) {
+      // MvNormal model on the lean path: kernel B of leaf j also materialises the first half of leaf j+1
+      const bool al_xpre = m->md.mv.aligned && mode == MODE_TREE && c->xpre;
+      if (j == 0 && !(al_xpre && c->pre_done)) hipLaunchKernelGGL(k_leaf_pre, dim3(A.nblk), dim3(VEC_THREADS), 0, s, A, io, j);
+      if (j == 0) c->pre_done = false;
+      io.pre_next = last ? 0 : 1;
+      if (last && al_xpre && c->defer_last_ctl && c->next_dir != 0) {
+        // the next doubling is queued right behind this leaf: same side -> its first leaf starts from this one (what pre_next = 1
+        // writes); other side -> from the tree's other edge state (pre_next = 3: k_leaf_pre's arithmetic on this workgroup's rows)
+        io.pre_next = c->next_dir == gm.dir ? 1 : 3;
+        c->pre_done = true;
+      }
     }
-    // row-aligned pass: as for the group-aligned row pass below, the control work of a doubling's LAST leaf rides in the first
-    // launch of the next doubling when the look-ahead queues that doubling right behind it (run_tree sets `defer_last_ctl`)
-    const bool al_tree_leaf = m->md.mv.aligned && mode == MODE_TREE;
-    CtlJob* job = (al_tree_leaf && j == 0 && c->pend_valid) ? &c->pend : nullptr;
+    // Row-aligned MvNormal pass and group-aligned row pass: the control work of a doubling's LAST leaf can ride in the first
+    // data pass of the next doubling when that doubling is queued by the look-ahead right behind it (run_tree sets
+    // `defer_last_ctl`): one launch less per doubling between two data passes.
+    const bool deferrable = (io.explicit_pre ? m->md.mv.aligned != 0 : m->md.lg.ga != 0) && mode == MODE_TREE;
+    CtlJob* job = (deferrable && j == 0 && c->pend_valid) ? &c->pend : nullptr;
+    // (group-aligned pass, growing on the same side: this leaf starts from the leaf just finished)
+    if (job && !io.explicit_pre) job->src_prev = job->io.dir == io.dir;
     launch_dense(m, A, io, j, (j > 0 || job) ? 1 : 0, d, c->cfg.Emax, max_depth, st, job);
     if (job) c->pend_valid = false;
     launch_vector(m, A, io, j, d);
     if (last) {
-      if (al_tree_leaf && c->defer_last_ctl) { c->pend = CtlJob{io, j, d, seq, false}; c->pend_valid = true; }
+      if (deferrable && c->defer_last_ctl) { c->pend = CtlJob{io, j, d, seq, false}; c->pend_valid = true; }
       else launch_control_lean(m, A, io, j, d, c->cfg.Emax, max_depth, st, seq);
     }
     c->leapfrogs++;
@@ -2862,29 +2986,6 @@ static inline void enqueue_leaf(nuts_chain* c, const Geometry& gm, int j, int d,
   if (io.explicit_pre) hipLaunchKernelGGL(k_leaf_pre, dim3(A.nblk), dim3(VEC_THREADS), 0, s, A, io, j);
   if (c->dense)   // v = C p_half ; q' = q + eps v   (integration.py:121-127 with a dense velocity)
     dense_velocity(c, A.P + d_o, A.V + d_o, A.Q + so, A.Q + d_o, gm.eps, abort_flag, VEL_ONLY);
-  if (io.lean && foldable) {
-    // folded control (kernels.h): the control work of leaf j-1 rides in workgroup 0 of this leaf's row pass; only the
-    // last leaf of the doubling (of the fixed-length trajectory) -- whose result the host waits for -- gets a control
-    // launch of its own
-    // Group-aligned row pass: the control work of a doubling's LAST leaf can ride in the first row pass of the next doubling
-    // when that doubling is queued by the look-ahead right behind it (run_tree sets `defer_last_ctl`): one launch less per
-    // doubling between two row passes.
-    const bool ga_tree_leaf = m->md.lg.ga && mode == MODE_TREE;
-    CtlJob* job = nullptr;
-    if (ga_tree_leaf && j == 0 && c->pend_valid) {
-      c->pend.src_prev = c->pend.io.dir == io.dir;   // growing on the same side: this leaf starts from the leaf just finished
-      job = &c->pend;
-    }
-    launch_dense(m, A, io, j, (j > 0 || job) ? 1 : 0, d, c->cfg.Emax, max_depth, st, job);
-    if (job) c->pend_valid = false;
-    launch_vector(m, A, io, j, d);
-    if (last) {
-      if (ga_tree_leaf && c->defer_last_ctl) { c->pend = CtlJob{io, j, d, seq, false}; c->pend_valid = true; }
-      else launch_control_lean(m, A, io, j, d, c->cfg.Emax, max_depth, st, seq);
-    }
-    c->leapfrogs++;
-    return;
-  }
   // (the group-aligned row pass finishes the leaf's z elements itself -- merges included -- so it needs `d` also when no
   // control work rides in it)
   launch_dense(m, A, io, j, 0, d, c->cfg.Emax, max_depth, st);
@@ -2910,7 +3011,6 @@ static inline void enqueue_leaf(nuts_chain* c, const Geometry& gm, int j, int d,
 // status word of its last leaf.  `uniforms`: the host copy of the pre-drawn `step.rng.random()` values of THIS draw.
 static int run_tree(nuts_chain* c, const double* uniforms, double step_size, int max_depth, unsigned* flags_out, bool* exhausted_out,
                     int* cursor_out = nullptr) {
-  using clk = std::chrono::steady_clock;
   int rc = NUTS_OK;
   bool exhausted = true;
   // (a chain whose leaves do not go through the row-aligned launch -- a dense mass matrix set after it joined -- is nobody's partner:
@@ -2972,7 +3072,7 @@ static int run_tree(nuts_chain* c, const double* uniforms, double step_size, int
     if (c->cb_err) return host_pot_error(c);
     const auto tw0 = clk::now();
     rc = wait_status(c, seq, &flags, cursor_out);
-    c->t_wait += std::chrono::duration<double>(clk::now() - tw0).count();
+    c->t_wait += secs(tw0, clk::now());
     if (rc) return rc;
     depth_done = d + 1;
     if (flags & ST_BAD_ENERGY) break;
@@ -3010,132 +3110,105 @@ static void launch_small(nuts_chain* c, const ArenaDev& A, const SmallDrawArgs& 
 // (a kernel), divergence bookkeeping, the statistics record.  `result_dev`: (q, grad) of the proposal on the device.
 static int finish_draw_host(nuts_chain* c, const DrawOut& o, bool adapt, bool exhausted, const double* result_dev, int64_t evals,
                             double perf_start, double perf_diff, double cpu_diff, nuts_draw_stats* stats) {
-  const int n = c->n;
-  ArenaDev& A = c->A;
-  const double accept = std::exp(o.log_accept_sum) / o.n_proposals;
-  c->da.update(accept, adapt);
+  c->da.update(std::exp(o.log_accept_sum) / o.n_proposals, adapt);
   int rc = potential_update(c, result_dev, result_dev + c->n);
   if (rc) return rc;
-  const bool diverging = o.diverging != 0;
-  if (diverging) {   // keep the leaf the integrator started from and the one it diverged to (base_hmc.py:249-258)
-    const int dir = o.div_t > 0 ? 1 : -1;   // a leaf's index is its parent's + sign(eps) and the start state is 0
-    c->div_source.resize(n); c->div_dest.resize(n);
-    HIPCHK(hipMemcpy(c->div_dest.data(), A.Q + (int64_t)(o.div_t & (A.S - 1)) * n, n * sizeof(double), hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(c->div_source.data(), A.Q + (int64_t)((o.div_t - dir) & (A.S - 1)) * n, n * sizeof(double), hipMemcpyDeviceToHost));
-  }
-  if (!c->tune) c->divergences += diverging;
+  if (o.diverging) { rc = read_divergence_points(c, o.div_t); if (rc) return rc; }
+  if (!c->tune) c->divergences += o.diverging != 0;
   c->iter_count += 1;
-  std::memset(stats, 0, sizeof(*stats));
-  stats->depth = o.depth;
-  stats->step_size = std::exp(c->da.log_step);
-  stats->step_size_bar = std::exp(c->da.log_bar);
-  stats->mean_tree_accept = accept;
-  stats->tree_size = o.n_proposals;
-  stats->diverging = diverging;
-  stats->reached_max_treedepth = (exhausted && !c->tune) ? 1 : 0;  // nuts.py:220-221
-  stats->divergences = c->divergences;
-  stats->energy_error = o.energy - o.E0;
-  stats->energy = o.energy;
-  stats->max_energy_error = o.max_energy_change;
-  stats->model_logp = o.logp;
-  stats->index_in_trajectory = o.proposal;
-  stats->n_uniforms_consumed = o.cursor;
-  stats->warning = diverging ? 1 : 0;
-  stats->divergence_energy_change = o.div_dE;
-  stats->n_model_evals = evals;
-  stats->perf_counter_start = perf_start;
-  stats->perf_counter_diff = perf_diff;
-  stats->process_time_diff = cpu_diff;
+  fill_draw_stats(c, o, exhausted, evals, perf_start, perf_diff, cpu_diff, stats);
+  return NUTS_OK;
+}
+
+// the arguments of the single-launch kernel that do not depend on how many draws it makes: start state (`cached`: the previous
+// proposal in out_dev2), step, limits, where the last proposal goes.  The caller adds normals, n_draws, n_uniforms, trace_q, out, n_done.
+static SmallDrawArgs small_draw_args(const nuts_chain* c, bool cached, const DrawPlan& plan) {
+  SmallDrawArgs a{};
+  a.q_src = cached ? c->out_dev2 : nullptr; a.g_src = cached ? c->out_dev2 + c->n : nullptr; a.cached_logp = c->last_logp;
+  a.step_size = plan.step_size; a.Emax = c->cfg.Emax; a.max_depth = plan.max_depth;
+  a.worst_uniforms = plan.need_uni;
+  a.q_out = c->out_dev; a.g_out = c->out_dev + c->n; a.st = nullptr; a.seq = 0; a.lds_slots = c->small_lds_slots;
+  return a;
+}
+
+// One transition, two ways.  Each leaves (q, grad) of the proposal in out_host and its record in do_host, and reports whether the
+// tree ran to its depth limit and where the proposal lies on the device.
+// Latency regime: the whole transition in one launch of one workgroup (small_kernel.h)
+static int draw_one_small(nuts_chain* c, const double* q0, const double* normals, const double* uniforms, const DrawPlan& plan,
+                          bool* exhausted, const double** result_dev) {
+  const int n = c->n;
+  hipStream_t s = c->m->stream;
+  ArenaDev& A = c->A;
+  const bool cached = start_cached(c, q0);
+  std::memcpy(c->stage_host, q0, n * sizeof(double));
+  std::memcpy(c->stage_host + n, normals, n * sizeof(double));
+  // (this path takes log(u) on the device, small_kernel.h: only the uniforms travel)
+  std::memcpy(c->stage_host + 2 * n, uniforms, plan.need_uni * sizeof(double));
+  HIPCHK(hipMemcpyAsync(c->stage_dev, c->stage_host, (2 * (size_t)n + plan.need_uni) * sizeof(double), hipMemcpyHostToDevice, s));
+  if (!cached) HIPCHK(hipMemcpyAsync(A.Q, c->stage_dev, n * sizeof(double), hipMemcpyDeviceToDevice, s));
+  SmallDrawArgs a = small_draw_args(c, cached, plan);
+  a.normals = c->stage_dev + n;
+  a.n_draws = 1; a.n_uniforms = plan.need_uni;
+  a.trace_q = nullptr; a.out = c->do_dev; a.n_done = nullptr;
+  launch_small(c, A, a);
+  // the next draw's start-state cache must not alias this draw's output buffer
+  std::swap(c->out_dev, c->out_dev2);
+  HIPCHK(hipMemcpyAsync(c->out_host, c->out_dev2, 2 * (size_t)n * sizeof(double), hipMemcpyDeviceToHost, s));
+  HIPCHK(hipMemcpyAsync(c->do_host, c->do_dev, sizeof(DrawOut), hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  HIPCHK(hipGetLastError());
+  if (c->do_host->bad_energy) return bad_initial_energy(c);
+  *exhausted = !(c->do_host->diverging || c->do_host->turning);
+  *result_dev = c->out_dev2;
+  return NUTS_OK;
+}
+// General path: the host in the doubling loop, one or more launches per leapfrog
+static int draw_one_general(nuts_chain* c, const double* q0, const double* normals, const double* uniforms, const DrawPlan& plan,
+                            clk::time_point t0, bool* exhausted, const double** result_dev) {
+  const int n = c->n;
+  hipStream_t s = c->m->stream;
+  int rc = draw_begin(c, q0, normals, uniforms, plan.need_uni, plan.step_size, plan.max_depth, false, 0, true);
+  if (rc) return rc;
+  const auto tb = clk::now();
+  c->t_begin += secs(t0, tb);
+  unsigned flags = 0;
+  rc = run_tree(c, uniforms, plan.step_size, plan.max_depth, &flags, exhausted);
+  if (rc) return rc;
+  const auto tl = clk::now();
+  c->t_loop += secs(tb, tl);
+  if (flags & ST_BAD_ENERGY) return bad_initial_energy(c);
+  const int fgrid = std::max(1, std::min(256, (n + VEC_THREADS - 1) / VEC_THREADS));
+  hipLaunchKernelGGL(k_draw_finish, dim3(fgrid), dim3(VEC_THREADS), 0, s, c->A, c->out_dev, c->out_dev + n, c->do_dev, (double*)nullptr,
+                     (DrawOutMapped*)nullptr, 0u);
+  HIPCHK(hipMemcpyAsync(c->out_host, c->out_dev, 2 * (size_t)n * sizeof(double), hipMemcpyDeviceToHost, s));
+  HIPCHK(hipMemcpyAsync(c->do_host, c->do_dev, sizeof(DrawOut), hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  HIPCHK(hipGetLastError());
+  c->t_finish += secs(tl, clk::now());
+  *result_dev = c->out_dev;
   return NUTS_OK;
 }
 
 extern "C" int nuts_chain_draw(nuts_chain* c, const double* q0, const double* normals, const double* uniforms,
                                int32_t n_uniforms, double* q_out, double* grad_out, nuts_draw_stats* stats) {
   if (!c || !q0 || !normals || !uniforms || !q_out || !stats) { g_err = "null argument"; return NUTS_E_ARG; }
-  using clk = std::chrono::steady_clock;
-  const auto t0 = clk::now();
-  const double perf_start = std::chrono::duration<double>(t0.time_since_epoch()).count();
-  const std::clock_t c0 = std::clock();
+  const DrawClock dclock;
   const int n = c->n;
-  hipStream_t s = c->m->stream;
-  ArenaDev& A = c->A;
-  // base_hmc.py:226-228 ; nuts.py:205-208
-  const bool adapt = c->tune && c->cfg.adapt_step_size;
-  const double step_size = c->da.current(adapt);
-  c->step_size = step_size;
-  const int max_depth = (c->tune && c->iter_count < 200) ? c->cfg.early_max_treedepth : c->cfg.max_treedepth;
-  const int need_uni = (1 << max_depth) + max_depth + 1;
-  if (n_uniforms < need_uni) { g_err = "not enough uniforms for the worst-case tree"; return NUTS_E_ARG; }
-
-  int rc = NUTS_OK;
+  const DrawPlan plan = plan_draw(c);
+  if (n_uniforms < plan.need_uni) { g_err = "not enough uniforms for the worst-case tree"; return NUTS_E_ARG; }
   bool exhausted = true;
-  int64_t evals = 1;
-  if (c->small) {
-    // latency regime: the whole transition in one launch of one workgroup (small_kernel.h)
-    const bool cached = c->cache_ok && c->cache_epoch == c->m->data_epoch && std::memcmp(q0, c->last_q.data(), n * sizeof(double)) == 0;
-    c->cache_ok = false;
-    std::memcpy(c->stage_host, q0, n * sizeof(double));
-    std::memcpy(c->stage_host + n, normals, n * sizeof(double));
-    // (this path takes log(u) on the device, small_kernel.h: only the uniforms travel)
-    std::memcpy(c->stage_host + 2 * n, uniforms, need_uni * sizeof(double));
-    HIPCHK(hipMemcpyAsync(c->stage_dev, c->stage_host, (2 * (size_t)n + need_uni) * sizeof(double), hipMemcpyHostToDevice, s));
-    if (!cached) HIPCHK(hipMemcpyAsync(A.Q, c->stage_dev, n * sizeof(double), hipMemcpyDeviceToDevice, s));
-    SmallDrawArgs a{};
-    a.normals = c->stage_dev + n;
-    a.q_src = cached ? c->out_dev2 : nullptr; a.g_src = cached ? c->out_dev2 + n : nullptr; a.cached_logp = c->last_logp;
-    a.step_size = step_size; a.Emax = c->cfg.Emax; a.max_depth = max_depth;
-    a.n_draws = 1; a.n_uniforms = need_uni; a.worst_uniforms = need_uni;
-    a.q_out = c->out_dev; a.g_out = c->out_dev + n; a.trace_q = nullptr; a.out = c->do_dev; a.n_done = nullptr; a.st = nullptr; a.seq = 0; a.lds_slots = c->small_lds_slots;
-    launch_small(c, A, a);
-    // the next draw's start-state cache must not alias this draw's output buffer
-    std::swap(c->out_dev, c->out_dev2);
-    HIPCHK(hipMemcpyAsync(c->out_host, c->out_dev2, 2 * (size_t)n * sizeof(double), hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(c->do_host, c->do_dev, sizeof(DrawOut), hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    HIPCHK(hipGetLastError());
-    if (c->do_host->bad_energy) {
-      rc = check_mass_matrix(c);
-      if (rc == NUTS_OK) g_err = "Bad initial energy, check any log probabilities that are inf or -inf, nan or very small";
-      return NUTS_E_BAD_ENERGY;
-    }
-    exhausted = !(c->do_host->diverging || c->do_host->turning);
-  } else {
-  rc = draw_begin(c, q0, normals, uniforms, need_uni, step_size, max_depth, false, 0, true);
+  const double* result_dev = nullptr;
+  int rc = c->small ? draw_one_small(c, q0, normals, uniforms, plan, &exhausted, &result_dev)
+                    : draw_one_general(c, q0, normals, uniforms, plan, dclock.t0, &exhausted, &result_dev);
   if (rc) return rc;
-  const auto tb = clk::now();
-  c->t_begin += std::chrono::duration<double>(tb - t0).count();
-  unsigned flags = 0;
-  rc = run_tree(c, uniforms, step_size, max_depth, &flags, &exhausted);
-  if (rc) return rc;
-  const auto tl = clk::now();
-  c->t_loop += std::chrono::duration<double>(tl - tb).count();
-  if (flags & ST_BAD_ENERGY) {
-    // base_hmc.py:205-224: SamplingError("Bad initial energy"), after potential.raise_ok
-    rc = check_mass_matrix(c);
-    if (rc == NUTS_OK) g_err = "Bad initial energy, check any log probabilities that are inf or -inf, nan or very small";
-    return NUTS_E_BAD_ENERGY;
-  }
-  const int fgrid = std::max(1, std::min(256, (n + VEC_THREADS - 1) / VEC_THREADS));
-  hipLaunchKernelGGL(k_draw_finish, dim3(fgrid), dim3(VEC_THREADS), 0, s, A, c->out_dev, c->out_dev + n, c->do_dev, (double*)nullptr,
-                     (DrawOutMapped*)nullptr, 0u);
-  HIPCHK(hipMemcpyAsync(c->out_host, c->out_dev, 2 * (size_t)n * sizeof(double), hipMemcpyDeviceToHost, s));
-  HIPCHK(hipMemcpyAsync(c->do_host, c->do_dev, sizeof(DrawOut), hipMemcpyDeviceToHost, s));
-  HIPCHK(hipStreamSynchronize(s));
-  HIPCHK(hipGetLastError());
-  c->t_finish += std::chrono::duration<double>(clk::now() - tl).count();
-  }
-  const double* const result_dev = c->small ? c->out_dev2 : c->out_dev;   // (q, grad) of the proposal on the device
   const DrawOut& o = *c->do_host;
-  evals += o.n_proposals;
-  const auto t1 = clk::now();
-  const std::clock_t c1 = std::clock();
-
-  rc = finish_draw_host(c, o, adapt, exhausted, result_dev, evals, perf_start, std::chrono::duration<double>(t1 - t0).count(),
-                        (double)(c1 - c0) / CLOCKS_PER_SEC, stats);
+  const int64_t evals = 1 + o.n_proposals;
+  const double wall = dclock.wall(), cpu = dclock.cpu();
+  rc = finish_draw_host(c, o, plan.adapt, exhausted, result_dev, evals, dclock.perf_start(), wall, cpu, stats);
   if (rc) return rc;
   std::memcpy(q_out, c->out_host, n * sizeof(double));
   if (grad_out) std::memcpy(grad_out, c->out_host + n, n * sizeof(double));
-  c->last_q.assign(c->out_host, c->out_host + n); c->last_logp = o.logp; c->cache_ok = true; c->cache_epoch = c->m->data_epoch;
+  commit_start_cache(c, c->out_host, o.logp);
   return NUTS_OK;
 }
 
@@ -3148,31 +3221,15 @@ extern "C" int nuts_chain_draw(nuts_chain* c, const double* q0, const double* no
 // not cover another worst-case tree; `stats[i].n_uniforms_consumed` is cumulative.
 static int draw_many_general(nuts_chain* c, const double* q0, const double* normals, const double* uniforms, int32_t n_uniforms,
                              int32_t K, double* q_out, nuts_draw_stats* stats, int32_t* n_done) {
-  using clk = std::chrono::steady_clock;
   const int n = c->n;
   hipStream_t s = c->m->stream;
   ArenaDev& A = c->A;
   const size_t U = (size_t)n_uniforms;
   const size_t in_doubles = (size_t)n + (size_t)K * n + 2 * U;
-  const size_t out_bytes = (size_t)K * n * sizeof(double);
-  if (in_doubles > c->many_in_cap || out_bytes > c->many_out_cap) {
-    HIPCHK(hipStreamSynchronize(s));
-    if (c->many_in_host) hipHostFree(c->many_in_host);
-    if (c->many_out_host) hipHostFree(c->many_out_host);
-    if (c->many_in_dev) hipFree(c->many_in_dev);
-    if (c->many_out_dev) hipFree(c->many_out_dev);
-    c->many_in_host = nullptr; c->many_out_host = nullptr; c->many_in_dev = nullptr; c->many_out_dev = nullptr;
-    c->many_in_cap = c->many_out_cap = 0;
-    HIPCHK(hipHostMalloc((void**)&c->many_in_host, in_doubles * sizeof(double), hipHostMallocDefault));
-    HIPCHK(hipHostMalloc((void**)&c->many_out_host, out_bytes, hipHostMallocDefault));
-    HIPCHK(hipMalloc((void**)&c->many_in_dev, in_doubles * sizeof(double)));
-    HIPCHK(hipMalloc((void**)&c->many_out_dev, out_bytes));
-    c->many_in_cap = in_doubles; c->many_out_cap = out_bytes;
-  }
+  int rc = ensure_many_staging(c, in_doubles, (size_t)K * n * sizeof(double));
+  if (rc) return rc;
   const auto tm0 = clk::now();
-  auto secs = [](clk::time_point a, clk::time_point b) { return std::chrono::duration<double>(b - a).count(); };
-  const bool cached0 = c->cache_ok && c->cache_epoch == c->m->data_epoch && std::memcmp(q0, c->last_q.data(), n * sizeof(double)) == 0;
-  c->cache_ok = false;
+  const bool cached0 = start_cached(c, q0);
   double* const h_q = c->many_in_host;
   double* const h_norm = h_q + n;
   double* const h_u = h_norm + (size_t)K * n;
@@ -3193,7 +3250,7 @@ static int draw_many_general(nuts_chain* c, const double* q0, const double* norm
   const double* const save_u = A.uniforms; const double* const save_lu = A.log_uniforms;
   const int save_done = c->logs_done, save_total = c->logs_total;
   c->logs_done = c->logs_total = 1 << 30;   // every logarithm of the batch is already on the device (ensure_logs has nothing to do)
-  int rc = NUTS_OK, done = 0;
+  int done = 0;
   size_t consumed = 0;
   const int fgrid = std::max(1, std::min(256, (n + VEC_THREADS - 1) / VEC_THREADS));
   c->tm_pre += secs(tm0, clk::now()); c->tm_batches++;
@@ -3203,42 +3260,28 @@ static int draw_many_general(nuts_chain* c, const double* q0, const double* norm
   // (the status) instead of three (status, record, then an idle queue to restart): ~50 us of GPU idle per draw on C2-S / C3
   // (profiles/r03g_profile_c3.txt: 50.7 us idle before k_draw_start).  A divergent draw is finished synchronously, as before.
   const bool pipe = !c->tune && !c->full_adapt && c->pipe_draws;   // (the option is latched when the chain is created)
-  struct Pending {
+  struct Pending {   // a draw whose finish kernel has been queued and whose record has not been read
     bool valid = false; int k = 0; unsigned seq = 0; bool exhausted = false, adapt = false; size_t consumed_after = 0; int cursor = 0;
     double perf_start = 0.0, wall = 0.0, cpu = 0.0;
   } pend;
-  auto enqueue_start = [&](int k, double step_size, int max_depth, bool from_prev) {   // momentum, start state, control block of draw k
-    if (c->dense) {
-      if (c->full_adapt) fa_random(c, d_norm + (size_t)k * n, A.P);
-      else hipLaunchKernelGGL(k_dense_mv, dim3(c->mv_grid), dim3(256), 0, s, c->dense_W, d_norm + (size_t)k * n, A.P, n, (const double*)nullptr,
-                         (double*)nullptr, 0.0, (const int*)nullptr);
-      hipLaunchKernelGGL(k_dense_mv, dim3(c->mv_grid), dim3(256), 0, s, c->dense_C, A.P, A.V, n, (const double*)nullptr, (double*)nullptr, 0.0,
-                         (const int*)nullptr);
-    }
-    hipLaunchKernelGGL(k_draw_start, dim3(A.nblk), dim3(VEC_THREADS), 0, s, A, d_norm + (size_t)k * n, (const double*)nullptr, c->kin_part,
-                       from_prev ? (const double*)c->out_dev : (const double*)nullptr,
-                       from_prev ? (const double*)(c->out_dev + n) : (const double*)nullptr, c->dense);
-    hipLaunchKernelGGL(k_draw_ctl_start, dim3(1), dim3(64), 0, s, A, c->kin_part, step_size, 0, max_depth, c->st_dev, from_prev ? 1 : 0,
-                       c->last_logp, k > 0 ? (const DrawOut*)c->do_dev : (const DrawOut*)nullptr);
+  // momentum, start state, control block of draw k; `from_prev`: from the previous proposal ((q, grad) in out_dev, logp in do_dev / last_logp)
+  auto enqueue_start = [&](int k, const DrawPlan& plan, size_t at, bool from_prev) {
+    A.uniforms = d_u + at; A.log_uniforms = d_lu + at;
+    return enqueue_draw_start(c, d_norm + (size_t)k * n, false, from_prev, plan.step_size, 0, plan.max_depth, k > 0 ? (const DrawOut*)c->do_dev : nullptr);
   };
-  // host side of a draw whose finish kernel has been queued: wait for its record, adaptation + statistics
+  // host side of such a draw: wait for its record, adaptation + statistics
   auto complete = [&](const Pending& p, bool* diverged) -> int {
     const auto tb = clk::now();
     DrawOutMapped* slot = c->dom_host + (p.seq % DOM_RING);
-    volatile unsigned long long* w = &slot->seq;
-    for (unsigned spins = 0; (unsigned)*w != p.seq; ++spins) {
-      if ((spins & 0xfffff) == 0xfffff) {
-        if (hipStreamQuery(s) == hipSuccess && (unsigned)*w != p.seq) { g_err = "k_draw_finish ended without publishing its record"; return NUTS_E_HIP; }
-        if (clk::now() - tb > std::chrono::seconds(60)) { g_err = "timed out waiting for the device"; return NUTS_E_HIP; }
-      }
-    }
-    std::atomic_thread_fence(std::memory_order_acquire);
+    unsigned long long seen = 0;
+    int r = wait_seq(c, &slot->seq, 0, p.seq, "k_draw_finish ended without publishing its record", &seen);
+    if (r) return r;
     const DrawOut o = slot->o;
     const auto t1 = clk::now();
     c->tm_record += secs(tb, t1);
     if (o.cursor != p.cursor) { g_err = "internal error: the status word and the draw record disagree on the uniforms consumed"; return NUTS_E_HIP; }
-    int r = finish_draw_host(c, o, p.adapt, p.exhausted, c->out_dev, o.n_proposals + ((p.k == 0 && !cached0) ? 1 : 0), p.perf_start, p.wall, p.cpu,
-                             stats + p.k);
+    r = finish_draw_host(c, o, p.adapt, p.exhausted, c->out_dev, o.n_proposals + ((p.k == 0 && !cached0) ? 1 : 0), p.perf_start, p.wall, p.cpu,
+                         stats + p.k);
     c->tm_host += secs(t1, clk::now()); c->tm_draws++;
     if (r) return r;
     stats[p.k].n_uniforms_consumed = (int32_t)p.consumed_after;
@@ -3249,37 +3292,30 @@ static int draw_many_general(nuts_chain* c, const double* q0, const double* norm
   };
   bool started = false;   // the start kernels of draw k are already in the queue (put there behind draw k - 1's finish kernel)
   for (int k = 0; k < K; ++k) {
-    const auto t0 = clk::now();
-    const double perf_start = std::chrono::duration<double>(t0.time_since_epoch()).count();
-    const std::clock_t c0 = std::clock();
-    const bool adapt = c->tune && c->cfg.adapt_step_size;
-    const double step_size = c->da.current(adapt);
-    c->step_size = step_size;
-    const int max_depth = (c->tune && c->iter_count < 200) ? c->cfg.early_max_treedepth : c->cfg.max_treedepth;
-    const size_t need_uni = ((size_t)1 << max_depth) + max_depth + 1;
+    const DrawClock dclock;
+    const DrawPlan plan = plan_draw(c);
+    const size_t need_uni = (size_t)plan.need_uni;
     if (!started) {
       if (U - consumed < need_uni) {
         if (k == 0) { g_err = "not enough uniforms for the worst-case tree"; rc = NUTS_E_ARG; }
         break;
       }
-      A.uniforms = d_u + consumed; A.log_uniforms = d_lu + consumed;
-      enqueue_start(k, step_size, max_depth, k > 0 || cached0);   // (from the previous proposal: (q, grad) in out_dev, logp in do_dev / last_logp)
+      rc = enqueue_start(k, plan, consumed, k > 0 || cached0);
+      if (rc) break;
     }
     started = false;
     unsigned flags = 0;
     bool exhausted = true;
     int cursor = 0;
     const auto ta = clk::now();
-    c->tm_start += secs(t0, ta);
-    rc = run_tree(c, h_u + consumed, step_size, max_depth, &flags, &exhausted, &cursor);
+    c->tm_start += secs(dclock.t0, ta);
+    rc = run_tree(c, h_u + consumed, plan.step_size, plan.max_depth, &flags, &exhausted, &cursor);
     const auto tb = clk::now();
     c->tm_tree += secs(ta, tb);
     if (rc) break;
     if (flags & ST_BAD_ENERGY) {
       if (pend.valid) { bool dv = false; rc = complete(pend, &dv); pend.valid = false; if (rc) break; }
-      rc = check_mass_matrix(c);
-      if (rc == NUTS_OK) g_err = "Bad initial energy, check any log probabilities that are inf or -inf, nan or very small";
-      rc = NUTS_E_BAD_ENERGY;
+      rc = bad_initial_energy(c);
       break;
     }
     const unsigned seq = ++c->dom_seq;
@@ -3287,15 +3323,13 @@ static int draw_many_general(nuts_chain* c, const double* q0, const double* norm
                        c->dom_dev + (seq % DOM_RING), seq);
     const size_t consumed_after = consumed + (size_t)cursor;
     if (pipe && !(flags & ST_DIVERGING) && k + 1 < K && U - consumed_after >= need_uni) {
-      A.uniforms = d_u + consumed_after; A.log_uniforms = d_lu + consumed_after;
-      enqueue_start(k + 1, step_size, max_depth, true);
+      rc = enqueue_start(k + 1, plan, consumed_after, true);
+      if (rc) break;
       started = true;
     }
     Pending cur;
-    cur.valid = true; cur.k = k; cur.seq = seq; cur.exhausted = exhausted; cur.adapt = adapt; cur.consumed_after = consumed_after; cur.cursor = cursor;
-    cur.perf_start = perf_start;
-    cur.wall = std::chrono::duration<double>(clk::now() - t0).count();
-    cur.cpu = (double)(std::clock() - c0) / CLOCKS_PER_SEC;
+    cur.valid = true; cur.k = k; cur.seq = seq; cur.exhausted = exhausted; cur.adapt = plan.adapt; cur.consumed_after = consumed_after; cur.cursor = cursor;
+    cur.perf_start = dclock.perf_start(); cur.wall = dclock.wall(); cur.cpu = dclock.cpu();
     bool diverged = false;
     if (pend.valid) { rc = complete(pend, &diverged); pend.valid = false; if (rc) break; }   // (draw k - 1: never divergent, see above)
     if (started) pend = cur;                                  // its record is read while draw k + 1 runs
@@ -3313,15 +3347,14 @@ static int draw_many_general(nuts_chain* c, const double* q0, const double* norm
   c->logs_done = save_done; c->logs_total = save_total;
   *n_done = done;
   const auto tm1 = clk::now();
-  struct PostTimer { nuts_chain* c; clk::time_point t; ~PostTimer() { c->tm_post += std::chrono::duration<double>(clk::now() - t).count(); } } post_timer{c, tm1};
+  struct PostTimer { nuts_chain* c; clk::time_point t; ~PostTimer() { c->tm_post += secs(t, clk::now()); } } post_timer{c, tm1};
   if (done > 0) {
     HIPCHK(hipMemcpyAsync(c->many_out_host, c->many_out_dev, (size_t)done * n * sizeof(double), hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
     HIPCHK(hipGetLastError());
     const double* trace_host = reinterpret_cast<const double*>(c->many_out_host);
     std::memcpy(q_out, trace_host, (size_t)done * n * sizeof(double));
-    c->last_q.assign(trace_host + (size_t)(done - 1) * n, trace_host + (size_t)done * n);
-    c->cache_ok = true; c->cache_epoch = c->m->data_epoch;
+    commit_start_cache(c, trace_host + (size_t)(done - 1) * n, c->last_logp);   // (its logp: left there by `complete`)
   } else {
     hipStreamSynchronize(s);
   }
@@ -3340,110 +3373,58 @@ extern "C" int nuts_chain_draw_many(nuts_chain* c, const double* q0, const doubl
   if (c->host_pot) { g_err = "nuts_chain_draw_many: a host potential is consulted between draws (random, update): one nuts_chain_draw per transition"; return NUTS_E_ARG; }
   if (!c->small) return draw_many_general(c, q0, normals, uniforms, n_uniforms, K, q_out, stats, n_done);
   if (c->tune) { g_err = "nuts_chain_draw_many: the chain is still tuning (the single-launch batch has no adaptation between its draws)"; return NUTS_E_ARG; }
-  using clk = std::chrono::steady_clock;
-  const auto t0 = clk::now();
-  const double perf_start = std::chrono::duration<double>(t0.time_since_epoch()).count();
-  const std::clock_t c0 = std::clock();
+  const DrawClock dclock;
   const int n = c->n;
   hipStream_t s = c->m->stream;
   ArenaDev& A = c->A;
-  const double step_size = c->da.current(false);   // exp(log_step_size_bar) (step_sizes.py:60-64)
-  c->step_size = step_size;
-  const int max_depth = c->cfg.max_treedepth;
-  const int need_uni = (1 << max_depth) + max_depth + 1;
-  if (n_uniforms < need_uni) { g_err = "not enough uniforms for the worst-case tree"; return NUTS_E_ARG; }
+  const DrawPlan plan = plan_draw(c);   // (not tuning: exp(log_step_size_bar) (step_sizes.py:60-64), cfg.max_treedepth)
+  if (n_uniforms < plan.need_uni) { g_err = "not enough uniforms for the worst-case tree"; return NUTS_E_ARG; }
   // staging: q0 | normals [K][n] | uniforms   ->  trace [K][n] | DrawOut [K] | n_done
   const size_t in_doubles = (size_t)n + (size_t)K * n + (size_t)n_uniforms;
-  const size_t out_bytes = (size_t)K * n * sizeof(double) + (size_t)K * sizeof(DrawOut) + 16;
-  if (in_doubles > c->many_in_cap || out_bytes > c->many_out_cap) {
-    HIPCHK(hipStreamSynchronize(s));
-    if (c->many_in_host) hipHostFree(c->many_in_host);
-    if (c->many_out_host) hipHostFree(c->many_out_host);
-    if (c->many_in_dev) hipFree(c->many_in_dev);
-    if (c->many_out_dev) hipFree(c->many_out_dev);
-    c->many_in_host = nullptr; c->many_out_host = nullptr; c->many_in_dev = nullptr; c->many_out_dev = nullptr;
-    c->many_in_cap = c->many_out_cap = 0;
-    HIPCHK(hipHostMalloc((void**)&c->many_in_host, in_doubles * sizeof(double), hipHostMallocDefault));
-    HIPCHK(hipHostMalloc((void**)&c->many_out_host, out_bytes, hipHostMallocDefault));
-    HIPCHK(hipMalloc((void**)&c->many_in_dev, in_doubles * sizeof(double)));
-    HIPCHK(hipMalloc((void**)&c->many_out_dev, out_bytes));
-    c->many_in_cap = in_doubles; c->many_out_cap = out_bytes;
-  }
-  const bool cached = c->cache_ok && c->cache_epoch == c->m->data_epoch && std::memcmp(q0, c->last_q.data(), n * sizeof(double)) == 0;
-  c->cache_ok = false;
+  const size_t trace_bytes = (size_t)K * n * sizeof(double), outs_bytes = (size_t)K * sizeof(DrawOut);
+  const size_t out_bytes = trace_bytes + outs_bytes + 16;
+  int rc = ensure_many_staging(c, in_doubles, out_bytes);
+  if (rc) return rc;
+  const bool cached = start_cached(c, q0);
   std::memcpy(c->many_in_host, q0, n * sizeof(double));
   std::memcpy(c->many_in_host + n, normals, (size_t)K * n * sizeof(double));
   std::memcpy(c->many_in_host + n + (size_t)K * n, uniforms, (size_t)n_uniforms * sizeof(double));
   HIPCHK(hipMemcpyAsync(c->many_in_dev, c->many_in_host, in_doubles * sizeof(double), hipMemcpyHostToDevice, s));
   if (!cached) HIPCHK(hipMemcpyAsync(A.Q, c->many_in_dev, n * sizeof(double), hipMemcpyDeviceToDevice, s));
-  double* trace_dev = reinterpret_cast<double*>(c->many_out_dev);
-  DrawOut* outs_dev = reinterpret_cast<DrawOut*>(c->many_out_dev + (size_t)K * n * sizeof(double));
-  int* ndone_dev = reinterpret_cast<int*>(c->many_out_dev + (size_t)K * n * sizeof(double) + (size_t)K * sizeof(DrawOut));
   ArenaDev Am = A;
   Am.uniforms = c->many_in_dev + n + (size_t)K * n;
-  SmallDrawArgs a{};
+  SmallDrawArgs a = small_draw_args(c, cached, plan);
   a.normals = c->many_in_dev + n;
-  a.q_src = cached ? c->out_dev2 : nullptr; a.g_src = cached ? c->out_dev2 + n : nullptr; a.cached_logp = c->last_logp;
-  a.step_size = step_size; a.Emax = c->cfg.Emax; a.max_depth = max_depth;
-  a.n_draws = K; a.n_uniforms = n_uniforms; a.worst_uniforms = need_uni;
-  a.q_out = c->out_dev; a.g_out = c->out_dev + n; a.trace_q = trace_dev; a.out = outs_dev; a.n_done = ndone_dev; a.st = nullptr; a.seq = 0; a.lds_slots = c->small_lds_slots;
+  a.n_draws = K; a.n_uniforms = n_uniforms;
+  a.trace_q = reinterpret_cast<double*>(c->many_out_dev);
+  a.out = reinterpret_cast<DrawOut*>(c->many_out_dev + trace_bytes);
+  a.n_done = reinterpret_cast<int*>(c->many_out_dev + trace_bytes + outs_bytes);
   launch_small(c, Am, a);
   std::swap(c->out_dev, c->out_dev2);   // (q, grad) of the last proposal: the next call's start-state cache
   HIPCHK(hipMemcpyAsync(c->many_out_host, c->many_out_dev, out_bytes, hipMemcpyDeviceToHost, s));
   HIPCHK(hipStreamSynchronize(s));
   HIPCHK(hipGetLastError());
   const double* trace_host = reinterpret_cast<const double*>(c->many_out_host);
-  const DrawOut* outs = reinterpret_cast<const DrawOut*>(c->many_out_host + (size_t)K * n * sizeof(double));
-  const int done = *reinterpret_cast<const int*>(c->many_out_host + (size_t)K * n * sizeof(double) + (size_t)K * sizeof(DrawOut));
+  const DrawOut* outs = reinterpret_cast<const DrawOut*>(c->many_out_host + trace_bytes);
+  const int done = *reinterpret_cast<const int*>(c->many_out_host + trace_bytes + outs_bytes);
   *n_done = done;
   if (done <= 0 || done > K) { g_err = "nuts_chain_draw_many: the device reported an impossible draw count"; return NUTS_E_HIP; }
-  if (outs[done - 1].bad_energy) {
-    int rc = check_mass_matrix(c);
-    if (rc == NUTS_OK) g_err = "Bad initial energy, check any log probabilities that are inf or -inf, nan or very small";
-    return NUTS_E_BAD_ENERGY;
-  }
-  const auto t1 = clk::now();
-  const std::clock_t c1 = std::clock();
-  const double wall = std::chrono::duration<double>(t1 - t0).count() / done;
-  const double cpu = (double)(c1 - c0) / CLOCKS_PER_SEC / done;
+  if (outs[done - 1].bad_energy) return bad_initial_energy(c);
+  const double wall = dclock.wall() / done, cpu = dclock.cpu() / done;
   for (int i = 0; i < done; ++i) {
     const DrawOut& o = outs[i];
-    const bool diverging = o.diverging != 0;
-    c->divergences += diverging;          // (not tuning: base_hmc.py:270-273)
+    c->divergences += o.diverging != 0;          // (not tuning: base_hmc.py:270-273)
     c->iter_count += 1;
-    nuts_draw_stats* st = stats + i;
-    std::memset(st, 0, sizeof(*st));
-    st->depth = o.depth;
-    st->step_size = std::exp(c->da.log_step);
-    st->step_size_bar = std::exp(c->da.log_bar);
-    st->mean_tree_accept = std::exp(o.log_accept_sum) / o.n_proposals;
-    st->tree_size = o.n_proposals;
-    st->diverging = diverging;
-    st->reached_max_treedepth = !(o.diverging || o.turning) ? 1 : 0;   // nuts.py:220-221 (tune is false here)
-    st->divergences = c->divergences;
-    st->energy_error = o.energy - o.E0;
-    st->energy = o.energy;
-    st->max_energy_error = o.max_energy_change;
-    st->model_logp = o.logp;
-    st->index_in_trajectory = o.proposal;
-    st->n_uniforms_consumed = o.cursor;
-    st->warning = diverging ? 1 : 0;
-    st->divergence_energy_change = o.div_dE;
-    st->n_model_evals = o.n_proposals + (i == 0 && !cached ? 1 : 0);
-    st->perf_counter_start = perf_start + i * wall;
-    st->perf_counter_diff = wall;
-    st->process_time_diff = cpu;
+    // (reached_max_treedepth, nuts.py:220-221: neither diverged nor turned)
+    fill_draw_stats(c, o, !(o.diverging || o.turning), o.n_proposals + (i == 0 && !cached ? 1 : 0), dclock.perf_start() + i * wall, wall, cpu, stats + i);
   }
   const DrawOut& last = outs[done - 1];
   if (last.diverging) {   // only the last draw of a batch can be divergent: its two points are still in the arena
-    const int dir = last.div_t > 0 ? 1 : -1;
-    c->div_source.resize(n); c->div_dest.resize(n);
-    HIPCHK(hipMemcpy(c->div_dest.data(), A.Q + (int64_t)(last.div_t & (A.S - 1)) * n, n * sizeof(double), hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(c->div_source.data(), A.Q + (int64_t)((last.div_t - dir) & (A.S - 1)) * n, n * sizeof(double), hipMemcpyDeviceToHost));
+    rc = read_divergence_points(c, last.div_t);
+    if (rc) return rc;
   }
   std::memcpy(q_out, trace_host, (size_t)done * n * sizeof(double));
-  c->last_q.assign(trace_host + (size_t)(done - 1) * n, trace_host + (size_t)done * n);
-  c->last_logp = last.logp; c->cache_ok = true; c->cache_epoch = c->m->data_epoch;
+  commit_start_cache(c, trace_host + (size_t)(done - 1) * n, last.logp);
   return NUTS_OK;
 }
 
@@ -3452,16 +3433,12 @@ extern "C" int nuts_chain_draw_hmc(nuts_chain* c, const double* q0, const double
                                    double path_length, int32_t max_steps, double* q_out, double* grad_out,
                                    nuts_hmc_stats* stats) {
   if (!c || !q0 || !normals || !uniforms || !q_out || !stats) { g_err = "null argument"; return NUTS_E_ARG; }
-  using clk = std::chrono::steady_clock;
-  const auto t0 = clk::now();
-  const std::clock_t c0 = std::clock();
+  const DrawClock dclock;
   const int n = c->n;
   hipStream_t s = c->m->stream;
   ArenaDev& A = c->A;
-  const bool adapt = c->tune && c->cfg.adapt_step_size;
-  double step_size = c->da.current(adapt);
-  c->step_size = step_size;
-  step_size = (0.85 + (1.15 - 0.85) * uniforms[0]) * step_size;  // `unif` step_rand, hmc.py:35-36
+  const DrawPlan plan = plan_draw(c);
+  const double step_size = (0.85 + (1.15 - 0.85) * uniforms[0]) * plan.step_size;  // `unif` step_rand, hmc.py:35-36
   int n_steps = std::max(1, (int)(path_length / step_size));
   n_steps = std::min<int>(max_steps, n_steps);
   // a fixed-length trajectory only ever needs its previous state: the arena is used as a ring (slot = index mod S), and what
@@ -3479,17 +3456,12 @@ extern "C" int nuts_chain_draw_hmc(nuts_chain* c, const double* q0, const double
   const int last = n_steps & (A.S - 1);
   HIPCHK(hipMemcpyAsync(c->out_host, A.Q + (int64_t)last * n, n * sizeof(double), hipMemcpyDeviceToHost, s));
   HIPCHK(hipMemcpyAsync(c->out_host + n, A.G + (int64_t)last * n, n * sizeof(double), hipMemcpyDeviceToHost, s));
-  rc = sync_status(c);
-  if (rc) return rc;
+  HIPCHK(hipStreamSynchronize(s));   // (the status record is host memory: a stream sync makes it current)
   HIPCHK(hipMemcpy(&Eh[0], start_keep + n, sizeof(double), hipMemcpyDeviceToHost));
   HIPCHK(hipMemcpy(&Eh[1], A.E + last, sizeof(double), hipMemcpyDeviceToHost));
   HIPCHK(hipMemcpy(&lph[0], start_keep + n + 1, sizeof(double), hipMemcpyDeviceToHost));
   HIPCHK(hipMemcpy(&lph[1], A.LOGP + last, sizeof(double), hipMemcpyDeviceToHost));
-  if (c->st_host->bad_energy) {
-    rc = check_mass_matrix(c);
-    if (rc == NUTS_OK) g_err = "Bad initial energy, check any log probabilities that are inf or -inf, nan or very small";
-    return NUTS_E_BAD_ENERGY;
-  }
+  if (c->st_host->bad_energy) return bad_initial_energy(c);
   bool div = false;
   if (!std::isfinite(Eh[1])) div = true;           // hmc.py:147-148
   double dE = Eh[1] - Eh[0];
@@ -3498,9 +3470,8 @@ extern "C" int nuts_chain_draw_hmc(nuts_chain* c, const double* q0, const double
   const double accept = std::min(1.0, std::exp(-dE));
   // hmc.py:162: `div_info is not None or rng.random() >= accept` -- the accept draw is NOT consumed on a divergence
   const bool accepted = !(div || uniforms[1] >= accept);
-  const auto t1 = clk::now();
-  const std::clock_t c1 = std::clock();
-  c->da.update(accept, adapt);
+  const double wall = dclock.wall(), cpu = dclock.cpu();
+  c->da.update(accept, plan.adapt);
   // (a rejected transition stays at q0, which is still in the staging buffer of this draw)
   const double* xsel = accepted ? (A.Q + (int64_t)last * n) : c->stage_dev;
   // (gradient at q0 on a rejection: the copy kept aside above -- slot 0 of the ring is overwritten once n_steps >= S)
@@ -3521,9 +3492,7 @@ extern "C" int nuts_chain_draw_hmc(nuts_chain* c, const double* q0, const double
   stats->accept = accept; stats->energy_error = dE; stats->energy = Eh[1]; stats->model_logp = lph[1];
   stats->path_length = path_length; stats->n_steps = n_steps; stats->divergences = c->divergences;
   stats->diverging = div; stats->accepted = accepted;
-  stats->perf_counter_start = std::chrono::duration<double>(t0.time_since_epoch()).count();
-  stats->perf_counter_diff = std::chrono::duration<double>(t1 - t0).count();
-  stats->process_time_diff = (double)(c1 - c0) / CLOCKS_PER_SEC;
+  stats->perf_counter_start = dclock.perf_start(); stats->perf_counter_diff = wall; stats->process_time_diff = cpu;
   return NUTS_OK;
 }
 
