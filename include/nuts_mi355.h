@@ -302,6 +302,9 @@ int64_t nuts_model_algorithmic_bytes(const nuts_model *m);
  *   "mvn_row_aligned" is the rows per workgroup of that pass (0: the two-kernel leapfrog), "rows_group_block" the groups per
  *                         workgroup of the group-block pass (0: not used), "mixture_workgroups" the grid of the mixture node's
  *                         row kernel (0: no such node),
+ *   "rows_packed"         1 when the model holds a packed copy of the group-aligned tiles (csrc/rows_pack.h) and its single-chain
+ *                         launch streams it; launches of a chain group keep reading the raw tiles, which stay next to it,
+ *   "rows_pack_build_s"   host seconds building that copy took when the model was created (0: none),
  *   "rows_waves", "lean", "single_workgroup_ok". */
 int nuts_model_get_scalar(const nuts_model *m, const char *name, double *out);
 

@@ -126,6 +126,7 @@ struct nuts_model {
   int n_chains = 0;            // chains created on this model
   int64_t pool_extra = 0;         // doubles behind the spec's data pool: (values, seed) of every derived vector
   int64_t orphan_elems = 0, factor_elems = 0;   // elements of the factors without an owning variable / of all factors (compile_spec)
+  double rows_pack_s = 0.0;                  // host seconds the packed copy of the tiles cost when the model was built
   int64_t rows_xt_len = 0, rows_y_len = 0;   // group-aligned row pass: elements of the tiled X / y copies (chain groups compare them)
   std::vector<LinDev> lins_host;   // linear predictors (dense node 5, lin_kernel.h) as uploaded by build_lins: launch_vector reads them per leapfrog
 
@@ -585,7 +586,8 @@ static void launch_dense(nuts_model* m, const ArenaDev& A, const EvalIO& io, int
       }
     } else {
       switch (md.lg.D) {
-        case 8: if (md.lg.ga_dx == 7) hipLaunchKernelGGL((k_rows_ga<8, 2, 7>), grid, block, 0, m->stream, ga);
+        case 8: if (md.lg.ga_pack) hipLaunchKernelGGL((k_rows_ga<8, 2, 7, 1>), grid, block, 0, m->stream, ga);
+                else if (md.lg.ga_dx == 7) hipLaunchKernelGGL((k_rows_ga<8, 2, 7>), grid, block, 0, m->stream, ga);
                 else hipLaunchKernelGGL((k_rows_ga<8, 2>), grid, block, 0, m->stream, ga); break;
         case 4: hipLaunchKernelGGL((k_rows_ga<4, 2>), grid, block, 0, m->stream, ga); break;
         case 2: hipLaunchKernelGGL((k_rows_ga<2, 2>), grid, block, 0, m->stream, ga); break;
@@ -1413,6 +1415,62 @@ static bool build_rows_group(nuts_model* m, const nuts_model_spec* s, const std:
   lg.Xt = m->keep(dev_upload(xt.data(), xt.size()));
   lg.y = m->keep(dev_upload(yy.data(), yy.size()));
   m->rows_xt_len = (int64_t)xt.size(); m->rows_y_len = (int64_t)yy.size();
+  // ---- packed copy of the tiles for the single-chain pass (rows_pack.h): 6400 B per tile instead of 7296 on a pass bound by
+  // the bytes it moves.  Eligible: D = 8 with the intercept elided, two rows per lane, every y 0 or 1, and at most 1e-3 of the
+  // stored values outside the best 16-binade exponent window (they travel raw, as exceptions).  NUTS_GA_PACK=0 keeps the raw
+  // tiles (A/B, tests); the raw tiles stay in any case for the chain-group kernels. ----
+  lg.ga_pack = 0; lg.ga_pack_ebase20 = 0; lg.Xp = nullptr; lg.ga_pcoff = nullptr; lg.ga_pstride_uni = 0; lg.ga_pexc_idx = nullptr; lg.ga_pexc = nullptr;
+  m->rows_pack_s = 0.0;
+  if (!gpw && D == 8 && DX == 7 && m->rows_rpl == 2 && env_int("NUTS_GA_PACK", 1) != 0) {
+    const auto t0 = std::chrono::steady_clock::now();
+    const RpPlan plan = rp_plan(s->rows_X, lg.N, D, 1, s->rows_y);
+    if (plan.eligible) {
+      constexpr int64_t PSKEW = 2240;   // dwords between chunks: 35 x 256 B, an odd multiple like GA_SKEW, and more than one tile (the slack a wave without tiles reads)
+      std::vector<int64_t> pcoff((size_t)lg.G * W, 0);
+      int64_t ppos = 0;
+      for (int g = 0; g < lg.G; ++g) {
+        const int64_t T = tile0[g + 1] - tile0[g];
+        for (int w = 0; w < W; ++w) {
+          pcoff[(size_t)g * W + w] = ppos;
+          ppos += ((int64_t)(w + 1) * T / W - (int64_t)w * T / W) * RP_TILE_DWORDS + PSKEW;
+        }
+      }
+      if (lg.ga_T_uni > 0) lg.ga_pstride_uni = (lg.ga_T_uni / W) * RP_TILE_DWORDS + PSKEW;
+      std::vector<uint32_t> xp((size_t)(ppos + RP_TILE_DWORDS), 0u);
+      std::vector<uint64_t> exc_idx((size_t)n_tiles + 1, 0);
+      std::vector<RpExc> exc;
+      std::vector<double> cols((size_t)RP_COLS * RP_ROWS);
+      std::vector<int8_t> ty(RP_ROWS);
+      for (int g = 0; g < lg.G; ++g) {
+        const int64_t T = tile0[g + 1] - tile0[g], ng = gptr[g + 1] - gptr[g];
+        for (int w = 0; w < W; ++w) {
+          const int64_t c0 = (int64_t)w * T / W, c2 = (int64_t)(w + 1) * T / W;
+          for (int64_t t = c0; t < c2; ++t) {
+            const int nvalid = (int)std::min<int64_t>(RP_ROWS, ng - t * RP_ROWS);
+            std::fill(cols.begin(), cols.end(), 0.0); std::fill(ty.begin(), ty.end(), (int8_t)0);
+            for (int r = 0; r < nvalid; ++r) {
+              const int64_t i = gptr[g] + t * RP_ROWS + r;
+              for (int c = 0; c < RP_COLS; ++c) cols[(size_t)c * RP_ROWS + r] = s->rows_X[i * D + 1 + c];
+              ty[r] = s->rows_y[i];
+            }
+            const size_t e0 = exc.size();
+            rp_pack_tile(cols.data(), ty.data(), nvalid, plan.elo, (uint32_t)(t - c0), &xp[(size_t)(pcoff[(size_t)g * W + w] + (t - c0) * RP_TILE_DWORDS)], exc);
+            exc_idx[(size_t)(tile0[g] + t)] = (uint64_t)e0 | ((uint64_t)(exc.size() - e0) << 32);
+          }
+        }
+      }
+      exc.push_back(RpExc{0, 0, 0, 0});   // (never an empty upload)
+      lg.Xp = m->keep(dev_upload(xp.data(), xp.size()));
+      lg.ga_pcoff = m->keep(dev_upload(pcoff.data(), pcoff.size()));
+      lg.ga_pexc_idx = m->keep(dev_upload(exc_idx.data(), exc_idx.size()));
+      lg.ga_pexc = m->keep(dev_upload(exc.data(), exc.size()));
+      lg.ga_pack_ebase20 = (uint32_t)plan.elo << 20;
+      // (the packed copy is a second copy of X: where the device cannot hold it, the pass streams the raw tiles)
+      lg.ga_pack = (lg.Xp && lg.ga_pcoff && lg.ga_pexc_idx && lg.ga_pexc) ? 1 : 0;
+      if (!lg.ga_pack) (void)hipGetLastError();   // the refused allocation is not an error of the model
+    }
+    m->rows_pack_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+  }
   lg.ga_coff = m->keep(dev_upload(coff.data(), coff.size()));
   lg.ga_tile0 = m->keep(dev_upload(tile0.data(), tile0.size()));
   lg.ga_part = m->keep(dev_alloc<double>((size_t)lg.G * PART_STRIDE));
@@ -1955,6 +2013,9 @@ extern "C" int nuts_model_get_scalar(const nuts_model* m, const char* name, doub
   const std::string k(name);
   if (k == "rows_group_aligned") *out = m->md.lg.ga;
   else if (k == "rows_group_block") *out = m->md.lg.ga_gpw;
+  // (a packed copy exists and the single-chain launch streams it; a chain group of this model runs k_rows_ga_multi on the raw tiles)
+  else if (k == "rows_packed") *out = m->md.lg.ga ? m->md.lg.ga_pack : 0;
+  else if (k == "rows_pack_build_s") *out = m->rows_pack_s;
   else if (k == "rows_aux_workgroups") *out = m->md.lg.ga ? m->md.lg.ga_naux : 0;
   else if (k == "mixture_workgroups") *out = m->md.has_mix ? m->md.mix.nwg : 0;
   else if (k == "glm_workgroups") *out = m->md.has_glm ? m->md.glm.nwg : 0;

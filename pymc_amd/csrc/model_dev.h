@@ -16,6 +16,7 @@
 #pragma once
 #include "device_math.h"
 #include "nuts_mi355.h"
+#include "rows_pack.h"
 
 #define MAX_BTERMS 8        // broadcast terms per model
 #define MAX_DERIVED 4       // derived vectors (NUTS_D_DERIVED factors) per model
@@ -126,6 +127,16 @@ struct RowsDev {  // hierarchical Bernoulli-logit node (rows sorted by group); s
   // interpreter over every element that is not a z element (ga_auxel of them) and leave one record each behind the ga_nblk block
   // partials: ga_nrec = ga_nblk + ga_naux records per launch.  ga_naux == 0: the closed forms (the benchmark's model).
   int32_t ga_naux, ga_nrec, ga_auxel, ga_pad2;
+  // Packed tiles (rows_pack.h; ga_pack = 1: `k_rows_ga<8, 2, 7, 1>` streams Xp instead of Xt / y, which stay for every other
+  // kernel): 1600 dwords per tile, chunk (g, w) at dword ga_pcoff[g W + w] (uniform geometry: chunk index * ga_pstride_uni).
+  // Values outside the exponent window are patched from ga_pexc; tile t of group g has the entries
+  // [start, start + count) given by ga_pexc_idx[ga_tile0[g] + t] = start | count << 32.
+  int32_t ga_pack; uint32_t ga_pack_ebase20;
+  const uint32_t* Xp;
+  const int64_t* ga_pcoff;
+  int64_t ga_pstride_uni;
+  const uint64_t* ga_pexc_idx;
+  const RpExc* ga_pexc;
   // closed forms of what the interpreter would evaluate for this model (checked by the spec compiler):
   double z_np_mu, z_np_inv_var, z_np_lognorm;   // z ~ Normal(mu0, s0) untransformed
   double mu_c[3];                               // mu ~ Normal(p1, .): {p1, 1/sigma, log sigma}

@@ -28,6 +28,7 @@
 // flag can flip while a launch is in flight, once more at the end of every draw (k_draw_finish).
 #pragma once
 #include "rows_kernel.h"
+#include "rows_pack.h"
 
 // the local part of a hyper-parameter element: what kernel B evaluates through the interpreter on the lean path
 // (transform_full + its own prior), here in closed form (the spec compiler only selects this path for mu ~ Normal,
@@ -144,8 +145,109 @@ __device__ __forceinline__ void ga_unpack(const GaTileRegs7& t, double (&xx)[8][
 #pragma unroll
   for (int dd = 1; dd < 8; ++dd) { xx[dd][0] = t.c[dd - 1].x; xx[dd][1] = t.c[dd - 1].y; }
 }
-template <int DX> struct GaTileSel { typedef GaTileRegs type; };
-template <> struct GaTileSel<7> { typedef GaTileRegs7 type; };
+__device__ __forceinline__ uint32_t ga_ybits(const GaTileRegs& t) { return t.y; }
+__device__ __forceinline__ uint32_t ga_ybits(const GaTileRegs7& t) { return t.y; }
+
+// ---- the seven stored columns as lossless 57-bit values (rows_pack.h): 6400 B per tile instead of 7296, 7 loads, 25 registers ----
+// Every load reads one contiguous block: six 1 KiB planes of four dwords per lane and one 256 B plane of one (a lane's 25 dwords:
+// the low dwords of its 14 slots, then its 352-bit string of high fields + y bits).  Chosen when the model is built (engine.hip,
+// build_rows_group); the decode rebuilds the stored fp64 bit for bit, so ga_tile sees the operands the raw tile would have given it.
+typedef uint32_t ga_v4u __attribute__((ext_vector_type(4)));
+struct GaTileRegsP { ga_v4u p[6]; uint32_t last; };
+
+struct GaPackOff { uint32_t v16, v4; };   // per-lane byte offsets into the 16 / 4 B-per-lane planes
+
+// the seven loads of a packed tile: %0 .. %6 the destinations, %7 / %8 the lane's offsets into the 16 / 4 B-per-lane planes,
+// %9 / %10 the tile's first dword and dword 1024 (ONE text for both requests below: they differ in their ordering operands only)
+#define GA_PACKED_LOADS                                   \
+  "s_nop 4\n\t"                                           \
+  "global_load_dwordx4 %0, %7, %9\n\t"                    \
+  "global_load_dwordx4 %1, %7, %9 offset:1024\n\t"        \
+  "global_load_dwordx4 %2, %7, %9 offset:2048\n\t"        \
+  "global_load_dwordx4 %3, %7, %9 offset:3072\n\t"        \
+  "global_load_dwordx4 %4, %7, %10\n\t"                   \
+  "global_load_dwordx4 %5, %7, %10 offset:1024\n\t"       \
+  "global_load_dword %6, %8, %10 offset:2048"
+
+__device__ __forceinline__ void ga_issue8(const uint32_t* base /* wave-uniform: first dword of the tile */, const GaPackOff& vo, GaTileRegsP& t) {
+  const uint32_t* base2 = base + 1024;   // planes 4 .. 6 (the immediate offset field is 13 bits, signed)
+  asm volatile(
+      GA_PACKED_LOADS
+      : "=&v"(t.p[0]), "=&v"(t.p[1]), "=&v"(t.p[2]), "=&v"(t.p[3]), "=&v"(t.p[4]), "=&v"(t.p[5]), "=&v"(t.last)
+      : "v"(vo.v16), "v"(vo.v4), "s"(base), "s"(base2)
+      : "memory");
+}
+
+// The same request inside the streaming loop, where `t` is being REPLACED.  An asm statement orders memory operations only, so
+// nothing in the language keeps a register-only consumer of the OLD tile above it; were one scheduled below, the old tile would
+// still be live at the request, the new one would get other registers and be copied into the loop-carried ones at the back-edge,
+// while its loads are in flight.  The sums the stage on the old tile produced are therefore named as inputs: every instruction
+// that reads the old tile comes before the request.  The raw requests above carry no such operands and rely on the scheduler
+// alone; tests/test_rows_ga_tile_registers.py holds all of them to it on the built code object (each tile in flight keeps ONE
+// set of destination registers).
+__device__ __forceinline__ void ga_issue8(const uint32_t* base, const GaPackOff& vo, GaTileRegsP& t, const double (&acc)[8], double lp) {
+  const uint32_t* base2 = base + 1024;
+  asm volatile(
+      GA_PACKED_LOADS
+      : "=&v"(t.p[0]), "=&v"(t.p[1]), "=&v"(t.p[2]), "=&v"(t.p[3]), "=&v"(t.p[4]), "=&v"(t.p[5]), "=&v"(t.last)
+      : "v"(vo.v16), "v"(vo.v4), "s"(base), "s"(base2),
+        "v"(acc[0]), "v"(acc[1]), "v"(acc[2]), "v"(acc[3]), "v"(acc[4]), "v"(acc[5]), "v"(acc[6]), "v"(acc[7]), "v"(lp)
+      : "memory");
+}
+
+template <int N>
+__device__ __forceinline__ void ga_wait8(GaTileRegsP& t) {
+  asm volatile("s_waitcnt vmcnt(%7)"
+               : "+v"(t.p[0]), "+v"(t.p[1]), "+v"(t.p[2]), "+v"(t.p[3]), "+v"(t.p[4]), "+v"(t.p[5]), "+v"(t.last)
+               : "i"(N));
+}
+
+// decode: low dword as stored, high dword from the slot's 25-bit field (at bit 25 slot of the lane's string: one funnel shift with
+// a compile-time amount) and the window's base exponent
+// (every element is named with compile-time indices: an array built from the members would be read back from the tile as
+// ONE wide load, and the tile would then live in scratch)
+template <int DW> __device__ __forceinline__ uint32_t ga_pdw(const GaTileRegsP& t) {   // dword DW of the lane's 25
+  if constexpr (DW < 24) return t.p[DW >> 2][DW & 3]; else return t.last;
+}
+template <int S> __device__ __forceinline__ uint32_t ga_plo(const GaTileRegsP& t) { return ga_pdw<S>(t); }
+template <int Q> __device__ __forceinline__ uint32_t ga_phi(const GaTileRegsP& t) { return ga_pdw<RP_SLOTS + Q>(t); }
+template <int S> __device__ __forceinline__ double ga_pslot(const GaTileRegsP& t, uint32_t ebase20) {
+  constexpr int q = (RP_FIELD_BITS * S) >> 5, r = (RP_FIELD_BITS * S) & 31;
+  uint32_t f;
+  if constexpr (r + RP_FIELD_BITS <= 32) f = ga_phi<q>(t) >> r;
+  else f = __builtin_amdgcn_alignbit(ga_phi<q + 1>(t), ga_phi<q>(t), r);
+  return __hiloint2double((int)rp_decode_hi(f, ebase20), (int)ga_plo<S>(t));
+}
+__device__ __forceinline__ void ga_unpack(const GaTileRegsP& t, uint32_t ebase20, double (&xx)[8][2]) {
+  xx[0][0] = 1.0; xx[0][1] = 1.0;
+#define GA_PCOL(C) xx[1 + C][0] = ga_pslot<2 * C>(t, ebase20); xx[1 + C][1] = ga_pslot<2 * C + 1>(t, ebase20);
+  GA_PCOL(0) GA_PCOL(1) GA_PCOL(2) GA_PCOL(3) GA_PCOL(4) GA_PCOL(5) GA_PCOL(6)
+#undef GA_PCOL
+}
+__device__ __forceinline__ uint32_t ga_ybits(const GaTileRegsP& t) { return ((t.last >> 30) & 1u) | ((t.last >> 31) << 8); }
+
+// Exceptions (values outside the window): the raw bits of (lane, slot) replace the decoded placeholder.  Everything here is
+// wave-uniform control and scalar loads (constant address space: lgkmcnt-counted, the vector-load count is not disturbed).
+typedef const __attribute__((address_space(4))) uint64_t ga_k64;
+typedef const __attribute__((address_space(4))) ga_v4u ga_k128;   // one RpExc: {tile, lane | slot << 8, low dword, high dword}
+__device__ __forceinline__ uint64_t ga_exc_range(const uint64_t* idx, int tile) { return ((ga_k64*)idx)[tile]; }   // start | count << 32
+__device__ __forceinline__ void ga_patch(const RpExc* list, uint64_t range, int lane, double (&xx)[8][2]) {
+  const uint32_t e0 = (uint32_t)range, e1 = e0 + (uint32_t)(range >> 32);
+  for (uint32_t e = e0; e < e1; ++e) {
+    const ga_v4u x = ((ga_k128*)list)[e];
+    const int L = (int)(x.y & 0xffu), sl = (int)(x.y >> 8);
+    const double v = __hiloint2double((int)x.w, (int)x.z);
+#pragma unroll
+    for (int s = 0; s < RP_SLOTS; ++s) {
+      const bool hit = lane == L && sl == s;
+      xx[1 + (s >> 1)][s & 1] = hit ? v : xx[1 + (s >> 1)][s & 1];
+    }
+  }
+}
+
+template <int DX, int PK = 0> struct GaTileSel { typedef GaTileRegs type; };
+template <> struct GaTileSel<7, 0> { typedef GaTileRegs7 type; };
+template <> struct GaTileSel<7, 1> { typedef GaTileRegsP type; };
 
 // one tile of SPAN = 64 RPL rows: forward (eta, log-lik) + backward (d/dbeta) in registers
 // ILV: the rows of a lane may be interleaved by the scheduler (rows_gal_kernel.h: a dependent fp64 fma issues every ~24 cycles, and
@@ -238,12 +340,14 @@ __device__ __forceinline__ void ga_hyper(const ModelDev& md, const QView& qv, in
 }
 
 // DX: stored columns of X per tile (D, or D - 1 = 7 when column 0 is identically 1; only with D = 8)
-template <int D, int RPL, int DX = D>
+// PK: the seven stored columns come as packed 57-bit values (rows_pack.h; R.Xp and its own chunk offsets)
+template <int D, int RPL, int DX = D, int PK = 0>
 __global__ __launch_bounds__(64 * GA_MAXW, 4) void k_rows_ga(GaArgs a) {
   constexpr int SPAN = WAVE * RPL;
   static_assert(DX == D || (D == 8 && DX == 7), "only the intercept column of an 8-column model is elided");
-  typedef typename GaTileSel<DX>::type Tile;
-  constexpr int LOADS = DX + 1;   // loads per tile: the stored columns + y
+  static_assert(!PK || (D == 8 && DX == 7 && RPL == 2), "packed tiles: seven stored columns, two rows per lane");
+  typedef typename GaTileSel<DX, PK>::type Tile;
+  constexpr int LOADS = PK ? 7 : DX + 1;   // loads per tile: the stored columns + y, or the seven planes of a packed tile
   const ModelDev& md = a.md;
   const ArenaDev& A = a.A;
   const EvalIO& io = a.io;
@@ -287,11 +391,13 @@ __global__ __launch_bounds__(64 * GA_MAXW, 4) void k_rows_ga(GaArgs a) {
 
   // ---- geometry of this wave's stream (no memory access when every group has the same number of rows) ----
   int T; int64_t ng, cbase;
-  if (R.ga_T_uni > 0) { T = R.ga_T_uni; ng = R.ga_ng_uni; cbase = (int64_t)(g * W + w) * R.ga_cstride_uni; }
+  int tg0;   // packed tiles: index of the group's first tile in the per-tile exception table
+  if (R.ga_T_uni > 0) { T = R.ga_T_uni; ng = R.ga_ng_uni; cbase = (int64_t)(g * W + w) * (PK ? R.ga_pstride_uni : R.ga_cstride_uni); tg0 = g * T; }
   else {
-    T = __builtin_amdgcn_readfirstlane(R.ga_tile0[g + 1] - R.ga_tile0[g]);
+    tg0 = __builtin_amdgcn_readfirstlane(R.ga_tile0[g]);
+    T = __builtin_amdgcn_readfirstlane(R.ga_tile0[g + 1]) - tg0;
     ng = __builtin_amdgcn_readfirstlane((int)(R.gptr[g + 1] - R.gptr[g]));
-    const int64_t cb = R.ga_coff[g * W + w];
+    const int64_t cb = (PK ? R.ga_pcoff : R.ga_coff)[g * W + w];
     cbase = ((int64_t)__builtin_amdgcn_readfirstlane((int)(cb >> 32)) << 32) | (uint32_t)__builtin_amdgcn_readfirstlane((int)(cb & 0xffffffffll));
   }
   // The wave's tiles (its chunk) are streamed in two halves whose order alternates between launches (the tail of the previous
@@ -301,7 +407,7 @@ __global__ __launch_bounds__(64 * GA_MAXW, 4) void k_rows_ga(GaArgs a) {
   const int n = c2 - c0;
   const int nA = (n + 1) / 2;                                   // tiles of the first half (chunk-local [0, nA)), second [nA, n)
   const int nsw = rev ? n - nA : nA;                            // position in the sequence where the second-streamed half starts
-  constexpr int64_t TS = (int64_t)DX * SPAN;                    // doubles per tile
+  constexpr int64_t TS = PK ? RP_TILE_DWORDS : (int64_t)DX * SPAN;   // doubles per tile (packed: dwords)
   auto local_at = [&](int i) { return rev ? (i < nsw ? nA + i : i - nsw) : i; };
   auto tile_at = [&](int i) { return cbase + (int64_t)local_at(i) * TS; };
   const int l_last = (c2 == T) ? n - 1 : -1;                    // chunk-local index of the group's last (zero-padded) tile, if it is here
@@ -311,7 +417,16 @@ __global__ __launch_bounds__(64 * GA_MAXW, 4) void k_rows_ga(GaArgs a) {
   uint32_t ya = 0, yb = 0;
   Tile ta, tb;
   // (a wave without tiles requests the chunk's first tile slot anyway: the layout keeps one tile of slack behind every chunk)
-  if constexpr (D == 8 && RPL == 2) {
+  uint64_t ea = 0, eb = 0;   // packed tiles: the exception ranges of the tiles in flight (scalar loads issued with the tiles)
+  const int te0 = tg0 + c0;
+  const GaPackOff vo{(uint32_t)lane * 16u, (uint32_t)lane * 4u};   // (packed tiles only)
+  if constexpr (PK) {
+    const int l1 = min(1, max(n - 1, 0));
+    ga_issue8(R.Xp + tile_at(0), vo, ta);
+    ga_issue8(R.Xp + tile_at(l1), vo, tb);
+    ea = ga_exc_range(R.ga_pexc_idx, te0 + local_at(0));
+    eb = ga_exc_range(R.ga_pexc_idx, te0 + local_at(l1));
+  } else if constexpr (D == 8 && RPL == 2) {
     const uint32_t voff16 = (uint32_t)lane * 16u, voff2 = (uint32_t)lane * 2u;
     const int64_t o0 = tile_at(0), o1 = tile_at(min(1, max(n - 1, 0)));
     ga_issue8(R.Xt + o0, R.y + o0 / DX, voff16, voff2, ta);
@@ -373,7 +488,34 @@ __global__ __launch_bounds__(64 * GA_MAXW, 4) void k_rows_ga(GaArgs a) {
       ga_tile<D, RPL>(X, Y, beta, local_at(I) == l_last ? n_last : SPAN, lane, acc, lp);     \
     }
     const int nm1 = n - 1;
-    if constexpr (D == 8 && RPL == 2) {
+    if constexpr (PK) {
+      // packed tiles: the same two-deep stream with 7 loads per tile; a tile's exception range arrives with it
+      const uint32_t ebase20 = R.ga_pack_ebase20;
+      auto issue = [&](int i, Tile& t, uint64_t& er) {
+        const int ii = min(i, nm1);
+        ga_issue8(R.Xp + tile_at(ii), vo, t, acc, lp);
+        er = ga_exc_range(R.ga_pexc_idx, te0 + local_at(ii));
+      };
+#define GA_PSTAGE(T, E, I)                                                                   \
+      {                                                                                      \
+        ga_wait8<LOADS>(T);                                                                  \
+        if ((I) == nsw) flush();                                                             \
+        double xx[8][2];                                                                     \
+        ga_unpack(T, ebase20, xx);                                                           \
+        const uint32_t yy = ga_ybits(T);                                                     \
+        if ((uint32_t)((E) >> 32) != 0) ga_patch(R.ga_pexc, E, lane, xx);                    \
+        ga_tile<8, 2>(xx, yy, beta, local_at(I) == l_last ? n_last : SPAN, lane, acc, lp);   \
+      }
+      for (int i = 0; i < n; i += 2) {
+        GA_PSTAGE(ta, ea, i)
+        if (i + 1 >= n) break;
+        issue(i + 2, ta, ea);
+        GA_PSTAGE(tb, eb, i + 1)
+        issue(i + 3, tb, eb);
+      }
+      ga_wait8<0>(ta); ga_wait8<0>(tb);
+#undef GA_PSTAGE
+    } else if constexpr (D == 8 && RPL == 2) {
       // hand-counted loads: two tiles in flight per wave; the requests past the end re-read the wave's last tile (an L2 hit) so that
       // every stage has exactly 9 younger loads behind the tile it waits for
       const uint32_t voff16 = (uint32_t)lane * 16u, voff2 = (uint32_t)lane * 2u;
@@ -387,7 +529,7 @@ __global__ __launch_bounds__(64 * GA_MAXW, 4) void k_rows_ga(GaArgs a) {
         if ((I) == nsw) flush();                                                             \
         double xx[8][2];                                                                     \
         ga_unpack(T, xx);                                                                    \
-        ga_tile<8, 2>(xx, T.y, beta, local_at(I) == l_last ? n_last : SPAN, lane, acc, lp); \
+        ga_tile<8, 2>(xx, ga_ybits(T), beta, local_at(I) == l_last ? n_last : SPAN, lane, acc, lp); \
       }
       for (int i = 0; i < n; i += 2) {
         GA_ASTAGE(ta, i)
