@@ -324,18 +324,169 @@ struct GaArgs {
 #include "rows_aux.h"
 
 // mu', sigma' of this leaf: lane l gets q' (`hval0`) and p_half (`hph0`) of hyper-parameter element l mod 2D.  GA_FOLD_SRC: the source
-// state is the leaf of the previous launch, whose mu / sigma gradient is finished here from that launch's records.
+// state is the leaf of the previous launch, whose mu / sigma gradient is finished here from that launch's records (`prev`: the
+// model's, lean_src, or a group member's own, gam_src).
 template <int D>
-__device__ __forceinline__ void ga_hyper(const ModelDev& md, const QView& qv, int fold, int par, int lane, double& hval0, double& hph0) {
-  const RowsDev& R = md.lg;
+__device__ __forceinline__ void ga_hyper(const RowsDev& R, const QView& qv, int fold, const LeanSrc prev, int lane, double& hval0, double& hph0) {
   if (fold & GA_FOLD_SRC) {
-    const LeanSrc prev = lean_src(md, par ^ 1);
     rows_hyper_fold_elem<D>(R, prev.part, prev.stride, prev.nblk, prev.def_loc, qv, lane, hval0, hph0);
   } else {
     const int e = lane % (2 * D);
     const int i = e < D ? R.off_mu + e : R.off_sigma + (e - D);
     if (qv.composed) { hph0 = qv.p_half(i); hval0 = fma(qv.eps, qv.var[i] * hph0, qv.q[i]); }
     else { hph0 = 0.0; hval0 = qv.q[i]; }
+  }
+}
+
+// ---- a group's prologue and everything after its stream: ONE copy for k_rows_ga, k_rows_ga_multi (rows_ga_multi_kernel.h) and
+// k_rows_gal (rows_gal_kernel.h) -- a chain in a group runs the code below on its own buffers, so it is bitwise the chain alone by
+// construction; the group-block pass (rows_gb_kernel.h) shares the pieces that are not about records crossing workgroups ----
+
+// z' and p_half of element `iz` of this leaf
+__device__ __forceinline__ void ga_z_state(const QView& qv, int iz, double& zq, double& zph) {
+  if (qv.composed) { zph = fma(qv.half, qv.g[iz], qv.p[iz]); zq = fma(qv.eps, qv.var[iz] * zph, qv.q[iz]); }
+  else { zph = 0.0; zq = qv.q[iz]; }
+}
+
+// mu_d', sigma_d' (constrained) of coordinate d = `dl` from the lanes of ga_hyper; beta_g,d = fma(s_lane, z', m_lane)
+template <int D>
+__device__ __forceinline__ void ga_hyper_lanes(const RowsDev& R, double hval0, int dl, double& m_lane, double& s_lane) {
+  m_lane = __shfl(hval0, dl);
+  const double sraw = __shfl(hval0, D + dl);
+  s_lane = R.sigma_tr == NUTS_TR_LOG ? exp(sraw) : sraw;
+}
+
+// z ~ Normal(mu0, s0) in closed form (continuous.py:526-532): the element's log-prior term and its complete gradient
+__device__ __forceinline__ void ga_z_prior(const RowsDev& R, double zq, double s_lane, double db, double& grad, double& lpz) {
+  const double r = zq - R.z_np_mu;
+  const double gx = -r * R.z_np_inv_var;
+  lpz = -0.5 * r * r * R.z_np_inv_var - R.z_np_lognorm;
+  grad = gx + s_lane * db;                                 // d/dz = prior + sigma_d * d/dbeta_d
+}
+
+// the hyper-parameter elements' local parts + their q' (lane e < 2D: element e; ONE wave does it for the launch -- with auxiliary
+// workgroups, they do); their log-prior terms go into `lpg`
+template <int D>
+__device__ __forceinline__ void ga_hyper_local(const RowsDev& R, const ArenaDev& A, const Leaf& lf, double* def_loc, int par, bool leaf,
+                                               int lane, double hval, double hph, double& lpg) {
+  const int e = lane;
+  const bool hact = e < 2 * D, is_mu = e < D;
+  double gx, dxdq, dj, lpd;
+  ga_def_local(R, is_mu, hval, gx, dxdq, dj, lpd);
+  lpg += wave_sum(hact ? lpd : 0.0);
+  if (hact) {
+    const int dd = is_mu ? e : e - D;
+    const int slot = (is_mu ? R.def_mu : R.def_sigma) + dd;
+    double2* loc = reinterpret_cast<double2*>(def_loc + (int64_t)par * 4 * MAX_DEFERRED) + 2 * slot;
+    loc[0] = make_double2(gx, dxdq);
+    loc[1] = make_double2(dj, hph);
+    if (leaf) A.Q[lf.d_o + (is_mu ? R.off_mu : R.off_sigma) + dd] = hval;
+  }
+}
+
+// The tail wave of a chain in workgroup g: the group's D z elements (lane = coordinate), the hyper-parameter elements' local parts,
+// leaf_post, the group's record and the block ticket -- on the chain's own arena, records `ga_part`, arrival counters `ga_ticket`
+// and local parts `def_loc` (the three pointers come by reference: every caller keeps them in LDS, and each is read where it is
+// used instead of being held in registers across leaf_post).  `lf`: the caller's resolve_leaf(io, A, j).  The five prologue
+// values of the lane (ga_hyper, ga_z_state, ga_hyper_lanes) come by value; `mpf`: the merge operands the caller requested before
+// its barrier, or nullptr.  s_info <- {last arriver of the block, m, last}.
+// TREE: the launch is a tree leaf (the group kernels run nothing else); otherwise io.mode decides -- MODE_PLAIN writes io.grad
+// and runs no leaf_post, MODE_SIMPLE builds no tree.
+template <int D, bool TREE>
+__device__ __forceinline__ void ga_tail_wave(const RowsDev& R, const ArenaDev& A, const EvalIO& io, double* const& ga_part, unsigned* const& ga_ticket,
+                                             double* const& def_loc, const Leaf& lf, int g, int W, int j, int par, int d,
+                                             const double (&s_acc)[GA_MAXW][2][D + 1], double* s_red, int* s_info,
+                                             double hval, double hph, double zq, double zph, double s_lane, const MergePrefetch* mpf) {
+  const int lane = threadIdx.x & (WAVE - 1);
+  const bool leaf = TREE || io.mode != MODE_PLAIN;
+  const bool tree = TREE || io.mode == MODE_TREE;
+  const int dl = lane % D;
+  const int iz = R.off_z + g * D + dl;
+  double db = 0.0, lpg = 0.0;
+  for (int ww = 0; ww < W; ++ww) { db += s_acc[ww][0][dl] + s_acc[ww][1][dl]; lpg += s_acc[ww][0][D] + s_acc[ww][1][D]; }
+  const bool zact = lane < D;
+  int idx[1] = {iz};
+  bool act[1] = {zact};
+  double grad[1] = {0.0}, ph[1] = {zph};
+  {
+    double lpz;
+    ga_z_prior(R, zq, s_lane, db, grad[0], lpz);
+    lpg += wave_sum(zact ? lpz : 0.0);
+    if (zact) {
+      if (leaf) { A.G[lf.d_o + iz] = grad[0]; A.Q[lf.d_o + iz] = zq; }
+      else io.grad[iz] = grad[0];
+    }
+  }
+  if (g == 0 && R.ga_naux == 0) ga_hyper_local<D>(R, A, lf, def_loc, par, leaf, lane, hval, hph, lpg);
+  int m = 0; bool last = false;
+  if (leaf) leaf_post<1>(A, lf, j, d, tree, idx, act, grad, ph, s_red, 1, m, last, tree ? mpf : nullptr, 0);   // (-> s_red[k]: the wave's own)
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+
+  // ---- this group's record, write-through ----
+  double* rec = ga_part + (int64_t)g * PART_STRIDE;
+  if (lane == 0) st_agent(rec + PART_LP, lpg);
+  if (zact) { st_agent(rec + PART_DMU + lane, db); st_agent(rec + PART_DSG + lane, db * zq); }
+  if (leaf) {
+    for (int k = lane; k < NDOT; k += WAVE)
+      if (dot_needed(k, m, last)) st_agent(rec + PART_DOT + k, s_red[k]);
+  }
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the record has left this CU before the ticket is taken
+
+  // ---- ticket: the block's last arriver sums the block's records in group order ----
+  const int blk = g / R.ga_bsz;
+  const int cnt = min(R.G, (blk + 1) * R.ga_bsz) - blk * R.ga_bsz;
+  unsigned old = 0;
+  if (lane == 0) old = __hip_atomic_fetch_add(&ga_ticket[blk], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  old = (unsigned)__builtin_amdgcn_readfirstlane((int)old);
+  const int is_last = (int)old + 1 == cnt;
+  if (is_last && lane == 0) __hip_atomic_store(&ga_ticket[blk], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  if (lane == 0) { s_info[0] = is_last; s_info[1] = m; s_info[2] = last ? 1 : 0; }
+}
+
+// slot q of the `nn` a record carries -> its place in the record: logp, d/dmu[D], d/dsigma[D], the dots of m merge levels, the six of `extend`
+template <int D>
+__device__ __forceinline__ int ga_need_slot(int q, int m) {
+  if (q < 1) return PART_LP;
+  if (q < 1 + D) return PART_DMU + (q - 1);
+  if (q < 1 + 2 * D) return PART_DSG + (q - 1 - D);
+  if (q < 1 + 2 * D + 1 + 6 * m) return PART_DOT + (q - 1 - 2 * D);
+  return PART_DOT + DOT_TOP + (q - 1 - 2 * D - 1 - 6 * m);
+}
+
+// The last arriver's workgroup: block partial of a chain = sum of the block's records, chunks of 8 groups, chunks in order, into
+// the chain's `ga_bpart` of launch parity `par` (every thread of the workgroup; s_info as ga_tail_wave left it; ends with the
+// stores: a caller with several chains separates them with a barrier)
+template <int D>
+__device__ __forceinline__ void ga_block_partial(const RowsDev& R, const double* ga_part, double* ga_bpart, int par, int g, bool leaf,
+                                                 const int* s_info, double (&s_cp)[GA_MAXCHUNK][PART_STRIDE]) {
+  const int tid = threadIdx.x;
+  const int m = s_info[1];
+  const bool last = s_info[2] != 0;
+  const int blk = g / R.ga_bsz, g0 = blk * R.ga_bsz;
+  const int cnt = min(R.G, g0 + R.ga_bsz) - g0;
+  const int nch = (cnt + 7) / 8;
+  const int nn = 1 + 2 * D + (leaf ? 1 + 6 * m + (last ? 6 : 0) : 0);
+  const int NT = (int)blockDim.x;
+  for (int p = tid; p < nn * nch; p += NT) {
+    const int c = p / nn, k = ga_need_slot<D>(p - c * nn, m);
+    const int gg0 = c * 8, gcnt = min(8, cnt - gg0);
+    const double* src = ga_part + (int64_t)(g0 + gg0) * PART_STRIDE + k;
+    double v[8];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) v[u] = ld_agent(src + (int64_t)min(u, gcnt - 1) * PART_STRIDE);
+    double sum = 0.0;
+#pragma unroll
+    for (int u = 0; u < 8; ++u) sum += (u < gcnt) ? v[u] : 0.0;
+    s_cp[c][k] = sum;
+  }
+  __syncthreads();
+  double* bp = ga_bpart + ((int64_t)par * R.ga_nrec + blk) * PART_STRIDE;
+  for (int q = tid; q < nn; q += NT) {
+    const int k = ga_need_slot<D>(q, m);
+    double sum = 0.0;
+    for (int c = 0; c < nch; ++c) sum += s_cp[c][k];
+    bp[k] = sum;
   }
 }
 
@@ -381,7 +532,7 @@ __global__ __launch_bounds__(64 * GA_MAXW, 4) void k_rows_ga(GaArgs a) {
   if (b >= R.G) {
     static_assert(GA_AUX_SCRATCH_DOUBLES(GA_MAXW) <= GA_MAXCHUNK * PART_STRIDE, "auxiliary scratch does not fit the chunk buffer");
     double hv, hp;
-    ga_hyper<D>(md, qv, fold, par, lane, hv, hp);
+    ga_hyper<D>(R, qv, fold, lean_src(md, par ^ 1), lane, hv, hp);
     const int aux_id = b - R.G;
     // (LDS lent from the block reduce's chunk buffer, which only a block's last arriver uses)
     ga_aux<4>((const GaArgs*)__builtin_amdgcn_kernarg_segment_ptr(), aux_id, hv, hp, &s_cp[0][0], GA_MAXW, s_auxprog,
@@ -446,17 +597,14 @@ __global__ __launch_bounds__(64 * GA_MAXW, 4) void k_rows_ga(GaArgs a) {
 
   // ---- prologue: mu', sigma' of this leaf (every wave), z' of this group ----
   double hval0, hph0;   // lane l: q' and p_half of hyper-parameter element l mod 2D
-  ga_hyper<D>(md, qv, fold, par, lane, hval0, hph0);
+  ga_hyper<D>(R, qv, fold, lean_src(md, par ^ 1), lane, hval0, hph0);
   const int dl = lane % D;
   const int iz = R.off_z + g * D + dl;
   double beta[D];
   {
-    double zq, zph;
-    if (qv.composed) { zph = fma(qv.half, qv.g[iz], qv.p[iz]); zq = fma(qv.eps, qv.var[iz] * zph, qv.q[iz]); }
-    else { zph = 0.0; zq = qv.q[iz]; }
-    const double m_lane = __shfl(hval0, dl);
-    const double sraw = __shfl(hval0, D + dl);
-    const double s_lane = R.sigma_tr == NUTS_TR_LOG ? exp(sraw) : sraw;
+    double zq, zph, m_lane, s_lane;
+    ga_z_state(qv, iz, zq, zph);
+    ga_hyper_lanes<D>(R, hval0, dl, m_lane, s_lane);
     const double bl = fma(s_lane, zq, m_lane);
 #pragma unroll
     for (int dd = 0; dd < D; ++dd) beta[dd] = readlane_d(bl, dd);
@@ -566,120 +714,25 @@ __device__ __forceinline__ void ga_tail(const GaArgs& T, int g, double (&s_acc)[
   const ArenaDev& A = T.A;
   const EvalIO& io = T.io;
   const RowsDev& R = md.lg;
-  const int j = T.j, par = T.par, d = T.d;
+  const int j = T.j;
   const int tid = threadIdx.x, lane = tid & (WAVE - 1), w = tid >> 6, W = (int)blockDim.x >> 6;
   Leaf lf; QView qv;
   resolve_leaf(io, A, j, lf, qv);
   const bool leaf = io.mode != MODE_PLAIN;
   const bool tree = io.mode == MODE_TREE;
-  const int dl = lane % D;
-  const int iz = R.off_z + g * D + dl;
   // the operands of the first merge levels belong to earlier leaves: wave 0 requests them as soon as its own stream is done,
   // before it waits for the other waves, so they are in flight during the combine
+  const int dl = lane % D;
+  const int iz = R.off_z + g * D + dl;
   MergePrefetch mpf;
   if (w == 0 && tree && !(R.ga_flags & GA_F_NOTAIL)) merge_prefetch(A, lf, j, iz, mpf);
   __syncthreads();
   if (R.ga_flags & GA_F_NOTAIL) return;
 
-  if (w == 0) {
-    // ---- wave 0: the group's D z elements (lane = coordinate) ----
-    const double hval = s_keep[0][lane], hph = s_keep[1][lane], zq = s_keep[2][lane], zph = s_keep[3][lane], s_lane = s_keep[4][lane];
-    double db = 0.0, lpg = 0.0;
-    for (int ww = 0; ww < W; ++ww) { db += s_acc[ww][0][dl] + s_acc[ww][1][dl]; lpg += s_acc[ww][0][D] + s_acc[ww][1][D]; }
-    const bool zact = lane < D;
-    int idx[1] = {iz};
-    bool act[1] = {zact};
-    double grad[1] = {0.0}, ph[1] = {zph};
-    {
-      const double r = zq - R.z_np_mu;                       // z ~ Normal(mu0, s0) in closed form (continuous.py:526-532)
-      const double gx = -r * R.z_np_inv_var;
-      const double lpz = -0.5 * r * r * R.z_np_inv_var - R.z_np_lognorm;
-      grad[0] = gx + s_lane * db;                            // d/dz = prior + sigma_d * d/dbeta_d
-      lpg += wave_sum(zact ? lpz : 0.0);
-      if (zact) {
-        if (leaf) { A.G[lf.d_o + iz] = grad[0]; A.Q[lf.d_o + iz] = zq; }
-        else io.grad[iz] = grad[0];
-      }
-    }
-    // the hyper-parameter elements' local parts + their q' (one workgroup does it for the launch; with auxiliary workgroups, they do)
-    if (g == 0 && R.ga_naux == 0) {
-      const int e = lane;
-      const bool hact = e < 2 * D, is_mu = e < D;
-      double gx, dxdq, dj, lpd;
-      ga_def_local(R, is_mu, hval, gx, dxdq, dj, lpd);
-      lpg += wave_sum(hact ? lpd : 0.0);
-      if (hact) {
-        const int dd = is_mu ? e : e - D;
-        const int slot = (is_mu ? R.def_mu : R.def_sigma) + dd;
-        double2* loc = reinterpret_cast<double2*>(md.def_loc + (int64_t)par * 4 * MAX_DEFERRED) + 2 * slot;
-        loc[0] = make_double2(gx, dxdq);
-        loc[1] = make_double2(dj, hph);
-        if (leaf) A.Q[lf.d_o + (is_mu ? R.off_mu : R.off_sigma) + dd] = hval;
-      }
-    }
-    int m = 0; bool last = false;
-    if (leaf) leaf_post<1>(A, lf, j, d, tree, idx, act, grad, ph, s_red, 1, m, last, tree ? &mpf : nullptr);
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-
-    // ---- this group's record, write-through ----
-    double* rec = R.ga_part + (int64_t)g * PART_STRIDE;
-    if (lane == 0) st_agent(rec + PART_LP, lpg);
-    if (zact) { st_agent(rec + PART_DMU + lane, db); st_agent(rec + PART_DSG + lane, db * zq); }
-    if (leaf) {
-      for (int k = lane; k < NDOT; k += WAVE)
-        if (dot_needed(k, m, last)) st_agent(rec + PART_DOT + k, s_red[k]);
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the record has left this CU before the ticket is taken
-
-    // ---- ticket: the block's last arriver sums the block's records in group order ----
-    const int blk = g / R.ga_bsz;
-    const int cnt = min(R.G, (blk + 1) * R.ga_bsz) - blk * R.ga_bsz;
-    unsigned old = 0;
-    if (lane == 0) old = __hip_atomic_fetch_add(&R.ga_ticket[blk], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    old = (unsigned)__builtin_amdgcn_readfirstlane((int)old);
-    const int is_last = (int)old + 1 == cnt;
-    if (is_last && lane == 0) __hip_atomic_store(&R.ga_ticket[blk], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (lane == 0) { s_info[0] = is_last; s_info[1] = m; s_info[2] = last ? 1 : 0; }
-  }
+  if (w == 0)
+    ga_tail_wave<D, false>(R, A, io, R.ga_part, R.ga_ticket, md.def_loc, lf, g, W, j, T.par, T.d, s_acc, s_red, s_info,
+                           s_keep[0][lane], s_keep[1][lane], s_keep[2][lane], s_keep[3][lane], s_keep[4][lane], &mpf);
   __syncthreads();
   if (!s_info[0]) return;
-
-  // ---- the last arriver's workgroup: block partial = sum of the block's records, chunks of 8 groups, chunks in order ----
-  {
-    const int m = s_info[1];
-    const bool last = s_info[2] != 0;
-    const int blk = g / R.ga_bsz, g0 = blk * R.ga_bsz;
-    const int cnt = min(R.G, g0 + R.ga_bsz) - g0;
-    const int nch = (cnt + 7) / 8;
-    const int nn = 1 + 2 * D + (leaf ? 1 + 6 * m + (last ? 6 : 0) : 0);
-    auto need_slot = [&](int q) {
-      if (q < 1) return PART_LP;
-      if (q < 1 + D) return PART_DMU + (q - 1);
-      if (q < 1 + 2 * D) return PART_DSG + (q - 1 - D);
-      if (q < 1 + 2 * D + 1 + 6 * m) return PART_DOT + (q - 1 - 2 * D);
-      return PART_DOT + DOT_TOP + (q - 1 - 2 * D - 1 - 6 * m);
-    };
-    const int NT = (int)blockDim.x;
-    for (int p = tid; p < nn * nch; p += NT) {
-      const int c = p / nn, k = need_slot(p - c * nn);
-      const int gg0 = c * 8, gcnt = min(8, cnt - gg0);
-      const double* src = R.ga_part + (int64_t)(g0 + gg0) * PART_STRIDE + k;
-      double v[8];
-#pragma unroll
-      for (int u = 0; u < 8; ++u) v[u] = ld_agent(src + (int64_t)min(u, gcnt - 1) * PART_STRIDE);
-      double sum = 0.0;
-#pragma unroll
-      for (int u = 0; u < 8; ++u) sum += (u < gcnt) ? v[u] : 0.0;
-      s_cp[c][k] = sum;
-    }
-    __syncthreads();
-    double* bp = R.ga_bpart + ((int64_t)par * R.ga_nrec + blk) * PART_STRIDE;
-    for (int q = tid; q < nn; q += NT) {
-      const int k = need_slot(q);
-      double sum = 0.0;
-      for (int c = 0; c < nch; ++c) sum += s_cp[c][k];
-      bp[k] = sum;
-    }
-  }
+  ga_block_partial<D>(R, R.ga_part, R.ga_bpart, T.par, g, leaf, s_info, s_cp);
 }

@@ -7,13 +7,13 @@
 // the same time (engine.hip, the chain group: each chain's host thread deposits its launch, the last one to arrive submits them
 // together): workgroup g streams the tiles of group g ONCE and evaluates every row under NC coefficient vectors (beta_g of each
 // chain in scalar registers, NC sets of gradient accumulators), then finishes the group's D z elements of every chain -- second
-// kick, v', merge dot products, the group's record, the ticket on the chain's own arrival counters -- exactly as the single-chain
-// kernel's tail does, one wave per chain.  Workgroups 0 .. GAM_MAXC-1 carry the control work each chain folds into its launch (a
+// kick, v', merge dot products, the group's record, the ticket on the chain's own arrival counters: that IS the single-chain
+// kernel's tail (ga_tail_wave, ga_block_partial of rows_ga_kernel.h on the chain's buffers), one wave per chain.  Workgroups 0 .. GAM_MAXC-1 carry the control work each chain folds into its launch (a
 // chain's always in workgroup `slot`, i.e. on the same XCD).
 //
 // A chain's numbers do not depend on its company: every fma of a row, every wave sum (the exchange tree of mvn_multi_kernel.h
-// reproduces `wave_sum`'s association order), every record and block partial is formed from the chain's own operands in the
-// single-chain kernel's order, so a chain in a group is BITWISE the chain run alone (tests/test_gpu_chain_group.py).
+// reproduces `wave_sum`'s association order), every record and block partial is formed from the chain's own operands by the
+// single-chain kernel's code, so a chain in a group is BITWISE the chain run alone (tests/test_gpu_chain_group.py).
 //
 // Chains keep their own arena, control block, uniform stream, status words, records, block partials, tickets and local parts
 // (`ga_part`, `ga_bpart`, `ga_ticket`, `def_loc` of the chain's own model handle): nothing is shared but the read-only node data
@@ -48,127 +48,6 @@ struct GaMultiArgs {
 
 __device__ __forceinline__ LeanSrc gam_src(const RowsDev& R, const GaLeafArgs& L, int par) {
   return LeanSrc{L.ga_bpart + (int64_t)par * R.ga_nrec * PART_STRIDE, PART_STRIDE, R.ga_nrec, L.def_loc + (int64_t)par * 4 * MAX_DEFERRED};
-}
-
-// ga_hyper (rows_ga_kernel.h) on a chain's own records
-template <int D>
-__device__ __forceinline__ void gam_hyper(const RowsDev& R, const GaLeafArgs& L, const QView& qv, int lane, double& hval0, double& hph0) {
-  if (L.fold & GA_FOLD_SRC) {
-    const LeanSrc prev = gam_src(R, L, L.par ^ 1);
-    rows_hyper_fold_elem<D>(R, prev.part, prev.stride, prev.nblk, prev.def_loc, qv, lane, hval0, hph0);
-  } else {
-    const int e = lane % (2 * D);
-    const int i = e < D ? R.off_mu + e : R.off_sigma + (e - D);
-    if (qv.composed) { hph0 = qv.p_half(i); hval0 = fma(qv.eps, qv.var[i] * hph0, qv.q[i]); }
-    else { hph0 = 0.0; hval0 = qv.q[i]; }
-  }
-}
-
-// The tail wave of chain `L` in workgroup g: the "wave 0" part of ga_tail on this chain's sums and buffers.
-template <int D, bool PF>
-__device__ __forceinline__ void gam_tail_wave(const ModelDev& md, const GaLeafArgs& L, int g, int W, const double (&s_acc)[GA_MAXW][2][D + 1],
-                                              double* s_red, int* s_info, const double (&s_keep)[5][WAVE], const MergePrefetch& mpf) {
-  const RowsDev& R = md.lg;
-  const ArenaDev& A = L.A;
-  const int lane = threadIdx.x & (WAVE - 1);
-  const int j = L.j, par = L.par, d = L.d;
-  Leaf lf; QView qv;
-  resolve_leaf(L.io, A, j, lf, qv);
-  const int dl = lane % D;
-  const int iz = R.off_z + g * D + dl;
-  const double hval = s_keep[0][lane], hph = s_keep[1][lane], zq = s_keep[2][lane], zph = s_keep[3][lane], s_lane = s_keep[4][lane];
-  double db = 0.0, lpg = 0.0;
-  for (int ww = 0; ww < W; ++ww) { db += s_acc[ww][0][dl] + s_acc[ww][1][dl]; lpg += s_acc[ww][0][D] + s_acc[ww][1][D]; }
-  const bool zact = lane < D;
-  int idx[1] = {iz};
-  bool act[1] = {zact};
-  double grad[1] = {0.0}, ph[1] = {zph};
-  {
-    const double r = zq - R.z_np_mu;                       // z ~ Normal(mu0, s0) in closed form (continuous.py:526-532)
-    const double gx = -r * R.z_np_inv_var;
-    const double lpz = -0.5 * r * r * R.z_np_inv_var - R.z_np_lognorm;
-    grad[0] = gx + s_lane * db;                            // d/dz = prior + sigma_d * d/dbeta_d
-    lpg += wave_sum(zact ? lpz : 0.0);
-    if (zact) { A.G[lf.d_o + iz] = grad[0]; A.Q[lf.d_o + iz] = zq; }
-  }
-  if (g == 0) {   // the hyper-parameter elements' local parts + their q' (one workgroup does it for the launch)
-    const int e = lane;
-    const bool hact = e < 2 * D, is_mu = e < D;
-    double gx, dxdq, dj, lpd;
-    ga_def_local(R, is_mu, hval, gx, dxdq, dj, lpd);
-    lpg += wave_sum(hact ? lpd : 0.0);
-    if (hact) {
-      const int dd = is_mu ? e : e - D;
-      const int slot = (is_mu ? R.def_mu : R.def_sigma) + dd;
-      double2* loc = reinterpret_cast<double2*>(L.def_loc + (int64_t)par * 4 * MAX_DEFERRED) + 2 * slot;
-      loc[0] = make_double2(gx, dxdq);
-      loc[1] = make_double2(dj, hph);
-      A.Q[lf.d_o + (is_mu ? R.off_mu : R.off_sigma) + dd] = hval;
-    }
-  }
-  int m = 0; bool last = false;
-  leaf_post<1>(A, lf, j, d, true, idx, act, grad, ph, s_red, 1, m, last, PF ? &mpf : nullptr, 0);
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-
-  // ---- this group's record, write-through ----
-  double* rec = L.ga_part + (int64_t)g * PART_STRIDE;
-  if (lane == 0) st_agent(rec + PART_LP, lpg);
-  if (zact) { st_agent(rec + PART_DMU + lane, db); st_agent(rec + PART_DSG + lane, db * zq); }
-  for (int k = lane; k < NDOT; k += WAVE)
-    if (dot_needed(k, m, last)) st_agent(rec + PART_DOT + k, s_red[k]);
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the record has left this CU before the ticket is taken
-
-  // ---- ticket: the block's last arriver sums the block's records in group order ----
-  const int blk = g / R.ga_bsz;
-  const int cnt = min(R.G, (blk + 1) * R.ga_bsz) - blk * R.ga_bsz;
-  unsigned old = 0;
-  if (lane == 0) old = __hip_atomic_fetch_add(&L.ga_ticket[blk], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  old = (unsigned)__builtin_amdgcn_readfirstlane((int)old);
-  const int is_last = (int)old + 1 == cnt;
-  if (is_last && lane == 0) __hip_atomic_store(&L.ga_ticket[blk], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  if (lane == 0) { s_info[0] = is_last; s_info[1] = m; s_info[2] = last ? 1 : 0; }
-}
-
-// The last arriver's workgroup: block partial of chain `L` = sum of the block's records, chunks of 8 groups, chunks in order
-// (every thread of the workgroup; ends with the stores, the caller separates two chains with a barrier)
-template <int D>
-__device__ __forceinline__ void gam_block_partial(const RowsDev& R, const GaLeafArgs& L, int g, const int* s_info, double (&s_cp)[GA_MAXCHUNK][PART_STRIDE]) {
-  const int tid = threadIdx.x;
-  const int m = s_info[1];
-  const bool last = s_info[2] != 0;
-  const int blk = g / R.ga_bsz, g0 = blk * R.ga_bsz;
-  const int cnt = min(R.G, g0 + R.ga_bsz) - g0;
-  const int nch = (cnt + 7) / 8;
-  const int nn = 1 + 2 * D + 1 + 6 * m + (last ? 6 : 0);
-  auto need_slot = [&](int q) {
-    if (q < 1) return PART_LP;
-    if (q < 1 + D) return PART_DMU + (q - 1);
-    if (q < 1 + 2 * D) return PART_DSG + (q - 1 - D);
-    if (q < 1 + 2 * D + 1 + 6 * m) return PART_DOT + (q - 1 - 2 * D);
-    return PART_DOT + DOT_TOP + (q - 1 - 2 * D - 1 - 6 * m);
-  };
-  const int NT = (int)blockDim.x;
-  for (int p = tid; p < nn * nch; p += NT) {
-    const int c = p / nn, k = need_slot(p - c * nn);
-    const int gg0 = c * 8, gcnt = min(8, cnt - gg0);
-    const double* src = L.ga_part + (int64_t)(g0 + gg0) * PART_STRIDE + k;
-    double v[8];
-#pragma unroll
-    for (int u = 0; u < 8; ++u) v[u] = ld_agent(src + (int64_t)min(u, gcnt - 1) * PART_STRIDE);
-    double sum = 0.0;
-#pragma unroll
-    for (int u = 0; u < 8; ++u) sum += (u < gcnt) ? v[u] : 0.0;
-    s_cp[c][k] = sum;
-  }
-  __syncthreads();
-  double* bp = L.ga_bpart + ((int64_t)L.par * R.ga_nrec + blk) * PART_STRIDE;
-  for (int q = tid; q < nn; q += NT) {
-    const int k = need_slot(q);
-    double sum = 0.0;
-    for (int c = 0; c < nch; ++c) sum += s_cp[c][k];
-    bp[k] = sum;
-  }
 }
 
 // One tile into registers with ORDINARY loads (the single-chain kernel's hand-counted `global_load_dwordx4` + `vmcnt(N)` keep two
@@ -253,15 +132,12 @@ __global__ __launch_bounds__(64 * GA_MAXW, OCC) void k_rows_ga_multi(ModelDev md
     Leaf lf; QView qv;
     resolve_leaf(L.io, L.A, L.j, lf, qv);
     double hval0, hph0;
-    gam_hyper<D>(R, L, qv, lane, hval0, hph0);
+    ga_hyper<D>(R, qv, L.fold, gam_src(R, L, L.par ^ 1), lane, hval0, hph0);
     const int dl = lane % D;
     const int iz = R.off_z + g * D + dl;
-    double zq, zph;
-    if (qv.composed) { zph = fma(qv.half, qv.g[iz], qv.p[iz]); zq = fma(qv.eps, qv.var[iz] * zph, qv.q[iz]); }
-    else { zph = 0.0; zq = qv.q[iz]; }
-    const double m_lane = __shfl(hval0, dl);
-    const double sraw = __shfl(hval0, D + dl);
-    const double s_lane = R.sigma_tr == NUTS_TR_LOG ? exp(sraw) : sraw;
+    double zq, zph, m_lane, s_lane;
+    ga_z_state(qv, iz, zq, zph);
+    ga_hyper_lanes<D>(R, hval0, dl, m_lane, s_lane);
     const double bl = fma(s_lane, zq, m_lane);
     if (lane < D) s_beta[c][lane] = bl;
     s_keep[c][0][lane] = hval0; s_keep[c][1][lane] = hph0; s_keep[c][2][lane] = zq; s_keep[c][3][lane] = zph; s_keep[c][4][lane] = s_lane;
@@ -364,14 +240,21 @@ __global__ __launch_bounds__(64 * GA_MAXW, OCC) void k_rows_ga_multi(ModelDev md
   __syncthreads();
   for (int c = w; c < NC; c += W) {
     if ((dead >> c) & 1) { if (lane == 0) s_info[c][0] = 0; continue; }
-    if (c == w) gam_tail_wave<D, true>(md, Tm.c[c], g, W, s_acc[c], s_red[c], s_info[c], s_keep[c], mpf);
-    else gam_tail_wave<D, false>(md, Tm.c[c], g, W, s_acc[c], s_red[c], s_info[c], s_keep[c], mpf);
+    const GaLeafArgs& L = Tm.c[c];
+    Leaf lf; QView qv;
+    resolve_leaf(L.io, L.A, L.j, lf, qv);
+    auto tail = [&](const MergePrefetch* pf) {   // (a compile-time pointer in either call: `mpf` stays in registers)
+      ga_tail_wave<D, true>(R, L.A, L.io, L.ga_part, L.ga_ticket, L.def_loc, lf, g, W, L.j, L.par, L.d, s_acc[c], s_red[c], s_info[c],
+                            s_keep[c][0][lane], s_keep[c][1][lane], s_keep[c][2][lane], s_keep[c][3][lane], s_keep[c][4][lane], pf);
+    };
+    if (c == w) tail(&mpf);
+    else tail(nullptr);
   }
   __syncthreads();
 #pragma unroll
   for (int c = 0; c < NC; ++c) {
     if (!s_info[c][0]) continue;            // (workgroup-uniform)
-    gam_block_partial<D>(R, Tm.c[c], g, s_info[c], s_cp);
+    ga_block_partial<D>(R, Tm.c[c].ga_part, Tm.c[c].ga_bpart, Tm.c[c].par, g, true, s_info[c], s_cp);
     __syncthreads();
   }
 }

@@ -20,8 +20,9 @@
 //     order, and the tail combines the 2 W half sums in the same order -- BITWISE the chain alone (tests/test_gpu_chain_group.py),
 //     whatever the company.
 //
-// Prologue, tail, records, tickets and block partials are those of rows_ga_multi_kernel.h on the chain's own buffers; the chain's
-// wave keeps its five per-lane prologue values in registers (the old kernel parked them in LDS for another wave to pick up).
+// Prologue, tail, records, tickets and block partials ARE the single-chain kernel's (ga_hyper, ga_z_state, ga_tail_wave,
+// ga_block_partial of rows_ga_kernel.h) on the chain's own buffers; the wave that ran a chain's prologue also runs its tail
+// and hands it the five per-lane prologue values (in k_rows_ga_multi another wave may pick them up).
 // Arguments: a chain's constant part (arena, record and ticket pointers) lives in device memory, uploaded when the chain is first
 // seen; the per-launch part travels in the kernarg segment -- eight chains' complete arguments would not fit its 4 KiB.
 #pragma once
@@ -72,72 +73,6 @@ __device__ __forceinline__ void gal_dma4(const void* gsrc, uint32_t lds_dst) {  
 template <int N>
 __device__ __forceinline__ void gal_wait() { asm volatile("s_waitcnt vmcnt(%0)" ::"i"(N) : "memory"); }
 __device__ __forceinline__ void gal_barrier() { asm volatile("s_barrier" ::: "memory"); }
-
-// The tail wave of chain `L` in workgroup g (gam_tail_wave with the prologue values in registers).
-template <int D>
-__device__ __forceinline__ void gal_tail_wave(const ModelDev& md, const GaLeafArgs& L, int g, int W, const double (&s_acc)[GA_MAXW][2][D + 1],
-                                              double* s_red, int* s_info, double hval, double hph, double zq, double zph, double s_lane,
-                                              const MergePrefetch& mpf) {
-  const RowsDev& R = md.lg;
-  const ArenaDev& A = L.A;
-  const int lane = threadIdx.x & (WAVE - 1);
-  const int j = L.j, par = L.par, d = L.d;
-  Leaf lf; QView qv;
-  resolve_leaf(L.io, A, j, lf, qv);
-  const int dl = lane % D;
-  const int iz = R.off_z + g * D + dl;
-  double db = 0.0, lpg = 0.0;
-  for (int ww = 0; ww < W; ++ww) { db += s_acc[ww][0][dl] + s_acc[ww][1][dl]; lpg += s_acc[ww][0][D] + s_acc[ww][1][D]; }
-  const bool zact = lane < D;
-  int idx[1] = {iz};
-  bool act[1] = {zact};
-  double grad[1] = {0.0}, ph[1] = {zph};
-  {
-    const double r = zq - R.z_np_mu;                       // z ~ Normal(mu0, s0) in closed form (continuous.py:526-532)
-    const double gx = -r * R.z_np_inv_var;
-    const double lpz = -0.5 * r * r * R.z_np_inv_var - R.z_np_lognorm;
-    grad[0] = gx + s_lane * db;                            // d/dz = prior + sigma_d * d/dbeta_d
-    lpg += wave_sum(zact ? lpz : 0.0);
-    if (zact) { A.G[lf.d_o + iz] = grad[0]; A.Q[lf.d_o + iz] = zq; }
-  }
-  if (g == 0) {   // the hyper-parameter elements' local parts + their q' (one workgroup does it for the launch)
-    const int e = lane;
-    const bool hact = e < 2 * D, is_mu = e < D;
-    double gx, dxdq, dj, lpd;
-    ga_def_local(R, is_mu, hval, gx, dxdq, dj, lpd);
-    lpg += wave_sum(hact ? lpd : 0.0);
-    if (hact) {
-      const int dd = is_mu ? e : e - D;
-      const int slot = (is_mu ? R.def_mu : R.def_sigma) + dd;
-      double2* loc = reinterpret_cast<double2*>(L.def_loc + (int64_t)par * 4 * MAX_DEFERRED) + 2 * slot;
-      loc[0] = make_double2(gx, dxdq);
-      loc[1] = make_double2(dj, hph);
-      A.Q[lf.d_o + (is_mu ? R.off_mu : R.off_sigma) + dd] = hval;
-    }
-  }
-  int m = 0; bool last = false;
-  leaf_post<1>(A, lf, j, d, true, idx, act, grad, ph, s_red, 1, m, last, &mpf, 0);
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-
-  // ---- this group's record, write-through ----
-  double* rec = L.ga_part + (int64_t)g * PART_STRIDE;
-  if (lane == 0) st_agent(rec + PART_LP, lpg);
-  if (zact) { st_agent(rec + PART_DMU + lane, db); st_agent(rec + PART_DSG + lane, db * zq); }
-  for (int k = lane; k < NDOT; k += WAVE)
-    if (dot_needed(k, m, last)) st_agent(rec + PART_DOT + k, s_red[k]);
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the record has left this CU before the ticket is taken
-
-  // ---- ticket: the block's last arriver sums the block's records in group order ----
-  const int blk = g / R.ga_bsz;
-  const int cnt = min(R.G, (blk + 1) * R.ga_bsz) - blk * R.ga_bsz;
-  unsigned old = 0;
-  if (lane == 0) old = __hip_atomic_fetch_add(&L.ga_ticket[blk], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  old = (unsigned)__builtin_amdgcn_readfirstlane((int)old);
-  const int is_last = (int)old + 1 == cnt;
-  if (is_last && lane == 0) __hip_atomic_store(&L.ga_ticket[blk], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  if (lane == 0) { s_info[0] = is_last; s_info[1] = m; s_info[2] = last ? 1 : 0; }
-}
 
 // D = 8 covariates, two rows per lane; DX stored columns (7: the intercept column is not stored).  Grid: GAL_MAXC control workgroups +
 // G group workgroups; block: NC waves, wave c = chain c of this launch.  OCC: waves per SIMD the register budget is sized for.
@@ -258,14 +193,11 @@ __global__ __launch_bounds__(64 * NC, OCC) void k_rows_gal(ModelDev md, const Ga
     resolve_leaf(L.io, L.A, L.j, lf, qv);
     double bl = 0.0;
     if (!dead) {
-      gam_hyper<D>(R, L, qv, lane, hval0, hph0);
+      ga_hyper<D>(R, qv, L.fold, gam_src(R, L, L.par ^ 1), lane, hval0, hph0);
       const int dl = lane % D;
-      const int iz = R.off_z + g * D + dl;
-      if (qv.composed) { zph = fma(qv.half, qv.g[iz], qv.p[iz]); zq = fma(qv.eps, qv.var[iz] * zph, qv.q[iz]); }
-      else { zph = 0.0; zq = qv.q[iz]; }
-      const double m_lane = __shfl(hval0, dl);
-      const double sraw = __shfl(hval0, D + dl);
-      s_lane = R.sigma_tr == NUTS_TR_LOG ? exp(sraw) : sraw;
+      double m_lane;
+      ga_z_state(qv, R.off_z + g * D + dl, zq, zph);
+      ga_hyper_lanes<D>(R, hval0, dl, m_lane, s_lane);
       bl = fma(s_lane, zq, m_lane);
     }
 #pragma unroll
@@ -356,13 +288,14 @@ __global__ __launch_bounds__(64 * NC, OCC) void k_rows_gal(ModelDev md, const Ga
     merge_prefetch(L.A, lf, L.j, R.off_z + g * D + lane % D, mpf);
     // (lanes >= 2 D: values nobody looks at -- hval / hph feed the hyper-parameter elements' lanes, zq / zph / s_lane the D z lanes)
     const int kl = lane < 2 * D ? lane : 0;
-    gal_tail_wave<D>(md, L, g, W, s_acc[w], s_red, s_info[w], s_keep[w][0][kl], s_keep[w][1][kl], s_keep[w][2][kl], s_keep[w][3][kl], s_keep[w][4][kl], mpf);
+    ga_tail_wave<D, true>(R, L.A, L.io, L.ga_part, L.ga_ticket, L.def_loc, lf, g, W, L.j, L.par, L.d, s_acc[w], s_red, s_info[w],
+                          s_keep[w][0][kl], s_keep[w][1][kl], s_keep[w][2][kl], s_keep[w][3][kl], s_keep[w][4][kl], &mpf);
   } else if (lane == 0) s_info[w][0] = 0;
   __syncthreads();
 #pragma unroll
   for (int c = 0; c < NC; ++c) {
     if (!s_info[c][0]) continue;            // (workgroup-uniform)
-    gam_block_partial<D>(R, s_L[c], g, s_info[c], s_cp);
+    ga_block_partial<D>(R, s_L[c].ga_part, s_L[c].ga_bpart, s_L[c].par, g, true, s_info[c], s_cp);
     __syncthreads();
   }
 }

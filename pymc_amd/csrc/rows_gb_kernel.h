@@ -157,8 +157,7 @@ __device__ __forceinline__ void gb_body(const ModelDev& md, const GbChain& a, in
   double zq_first = 0.0, zph_first = 0.0;
   {
     const int izf = R.off_z + min(g0 + w, R.G - 1) * D + (lane % D);
-    if (qv.composed) { zph_first = fma(qv.half, qv.g[izf], qv.p[izf]); zq_first = fma(qv.eps, qv.var[izf] * zph_first, qv.q[izf]); }
-    else zq_first = qv.q[izf];
+    ga_z_state(qv, izf, zq_first, zph_first);
   }
   __syncthreads();
   double hval0, hph0;   // lane l: q' and p_half of hyper-parameter element l mod 2D
@@ -173,9 +172,8 @@ __device__ __forceinline__ void gb_body(const ModelDev& md, const GbChain& a, in
     else { hph0 = 0.0; hval0 = qv.q[hi]; }
   }
   const int dl = lane % D;
-  const double m_lane = __shfl(hval0, dl);
-  const double sraw = __shfl(hval0, D + dl);
-  const double s_lane = R.sigma_tr == NUTS_TR_LOG ? exp(sraw) : sraw;
+  double m_lane, s_lane;
+  ga_hyper_lanes<D>(R, hval0, dl, m_lane, s_lane);
   if (aborted) return;
   if (b >= R.ga_nblk) {   // auxiliary workgroup (rows_aux.h): everything of the model that is not a z element
     static_assert(GA_AUX_SCRATCH_DOUBLES(GB_W) <= GB_MAXGPW * PART_STRIDE, "auxiliary scratch does not fit the record buffer");
@@ -196,10 +194,7 @@ __device__ __forceinline__ void gb_body(const ModelDev& md, const GbChain& a, in
     const int iz = R.off_z + g * D + dl;
     // z' of this group and beta_g
     double zq = zq_first, zph = zph_first;
-    if (gl != w) {
-      if (qv.composed) { zph = fma(qv.half, qv.g[iz], qv.p[iz]); zq = fma(qv.eps, qv.var[iz] * zph, qv.q[iz]); }
-      else { zph = 0.0; zq = qv.q[iz]; }
-    }
+    if (gl != w) ga_z_state(qv, iz, zq, zph);
     MergePrefetch mpf;
     if (tree) merge_prefetch(A, lf, j, iz, mpf);   // operands of the first merge levels: in flight during the stream
     double beta[D];
@@ -235,31 +230,15 @@ __device__ __forceinline__ void gb_body(const ModelDev& md, const GbChain& a, in
     bool act[1] = {zact};
     double grad[1] = {0.0}, ph[1] = {zph};
     {
-      const double r = zq - R.z_np_mu;                       // z ~ Normal(mu0, s0) in closed form (continuous.py:526-532)
-      const double gx = -r * R.z_np_inv_var;
-      const double lpz = -0.5 * r * r * R.z_np_inv_var - R.z_np_lognorm;
-      grad[0] = gx + s_lane * db;                            // d/dz = prior + sigma_d * d/dbeta_d
+      double lpz;
+      ga_z_prior(R, zq, s_lane, db, grad[0], lpz);
       lpg += wave_sum8(zact ? lpz : 0.0);
       if (zact) {
         if (leaf) { A.G[lf.d_o + iz] = grad[0]; A.Q[lf.d_o + iz] = zq; }
         else io.grad[iz] = grad[0];
       }
     }
-    if (g == 0 && R.ga_naux == 0) {   // the hyper-parameter elements' local parts + their q' (one wave does it for the launch; with auxiliary workgroups, they do)
-      const int e = lane;
-      const bool hact = e < 2 * D, is_mu = e < D;
-      double gx, dxdq, dj, lpd;
-      ga_def_local(R, is_mu, hval0, gx, dxdq, dj, lpd);
-      lpg += wave_sum(hact ? lpd : 0.0);
-      if (hact) {
-        const int dd = is_mu ? e : e - D;
-        const int slot = (is_mu ? R.def_mu : R.def_sigma) + dd;
-        double2* loc = reinterpret_cast<double2*>(a.def_loc + (int64_t)par * 4 * MAX_DEFERRED) + 2 * slot;
-        loc[0] = make_double2(gx, dxdq);
-        loc[1] = make_double2(dj, hph0);
-        if (leaf) A.Q[lf.d_o + (is_mu ? R.off_mu : R.off_sigma) + dd] = hval0;
-      }
-    }
+    if (g == 0 && R.ga_naux == 0) ga_hyper_local<D>(R, A, lf, a.def_loc, par, leaf, lane, hval0, hph0, lpg);
     TICK(md, tk && gl == w, 4);
     if (leaf && !GB_XF(GB_F_NOPOST))
       leaf_post<1, false, D <= 8>(A, lf, j, d, tree, idx, act, grad, ph, &s_red[w][0], 1, m, last, tree ? &mpf : nullptr, 0);
@@ -286,12 +265,7 @@ __device__ __forceinline__ void gb_body(const ModelDev& md, const GbChain& a, in
     const int npad = (R.ga_nrec + WAVE - 1) / WAVE * WAVE;            // slot-major: bp[k * npad + b] (lean_src)
     double* bp = a.ga_bpart + (int64_t)par * PART_STRIDE * npad + b;
     for (int q = tid; q < nn; q += (int)blockDim.x) {
-      int k;
-      if (q < 1) k = PART_LP;
-      else if (q < 1 + D) k = PART_DMU + (q - 1);
-      else if (q < 1 + 2 * D) k = PART_DSG + (q - 1 - D);
-      else if (q < 1 + 2 * D + 1 + 6 * mm) k = PART_DOT + (q - 1 - 2 * D);
-      else k = PART_DOT + DOT_TOP + (q - 1 - 2 * D - 1 - 6 * mm);
+      const int k = ga_need_slot<D>(q, mm);
       double sum = 0.0;
       for (int gl = 0; gl < cnt; ++gl) sum += s_rec[gl][k];
       bp[(int64_t)k * npad] = sum;
