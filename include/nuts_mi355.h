@@ -273,6 +273,15 @@ int nuts_set_option(const char *name, int32_t value);
 int nuts_unset_option(const char *name);   /* back to the default of that one option */
 void nuts_clear_options(void);
 
+/* Edge pairing (option NUTS_EDGE_PAIR): the host-side plan of which launch of a tree also evaluates a leaf of the
+ * trajectory's other end (kind 1, "paired") and which leaf later starts from such a result instead of streaming X (kind 2,
+ * "replay").  Pure host logic, exposed for the tests: a tree that runs doublings 0 .. n_doublings-1 in directions dirs[d]
+ * (+1 / -1; n_dirs >= n_doublings directions are known from the draw's uniforms), look-ahead depth `spec`, depth limit
+ * `max_depth`, a ring of `ring` parked leaves.  out[5 i .. 5 i + 4] = {d, j, kind, ring slot or -1, index of the paired / replayed
+ * leaf in its end's sequence or -1} of launch i, in launch order.  Returns the number of launches, -1 on a bad argument. */
+int64_t nuts_edge_pair_plan(const int32_t *dirs, int32_t n_dirs, int32_t n_doublings, int32_t spec, int32_t max_depth,
+                            int32_t ring, int32_t *out, int64_t out_cap);
+
 int nuts_device_count(void);
 int nuts_set_device(int device);
 const char *nuts_last_error(void);
@@ -305,6 +314,12 @@ int64_t nuts_model_algorithmic_bytes(const nuts_model *m);
  *   "rows_packed"         1 when the model holds a packed copy of the group-aligned tiles (csrc/rows_pack.h) and its single-chain
  *                         launch streams it; launches of a chain group keep reading the raw tiles, which stay next to it,
  *   "rows_pack_build_s"   host seconds building that copy took when the model was created (0: none),
+ *   "edge_pair"           1 when the model is eligible for edge pairing (the single-chain group-aligned pass of the closed-form
+ *                         hierarchical-logit model) and NUTS_EDGE_PAIR was not 0 when it was created; "edge_pair_ring_bytes" the
+ *                         size of its ring; "edge_pair_shadows" / "edge_pair_replays" the leaves evaluated ahead / replayed so far,
+ *                         "edge_pair_turns" the most changes of direction between the doublings of one tree of depth >= 4 so far,
+ *                         "edge_pair_dropped" the leaves evaluated ahead for a doubling their tree never reached,
+ *                         "edge_pair_ring_full" the leaves that streamed alone only because the ring had no room,
  *   "rows_waves", "lean", "single_workgroup_ok". */
 int nuts_model_get_scalar(const nuts_model *m, const char *name, double *out);
 

@@ -268,6 +268,7 @@ SYMBOLS = {
     "nuts_gibbs_sweep_prop": (C.c_int, [_VP, _VP, _VP, _PD, _PD, _PD, _VP, _PD, _PD, _VP, C.POINTER(C.c_int64), _PD, _PD, _PD]),
     "nuts_set_option": (C.c_int, [C.c_char_p, C.c_int32]),
     "nuts_clear_options": (None, []),
+    "nuts_edge_pair_plan": (C.c_int64, [C.POINTER(C.c_int32), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.c_int64]),
     "nuts_advi_create": (_VP, [C.POINTER(AdviConfig)]),
     "nuts_advi_destroy": (None, [_VP]),
     "nuts_advi_steps": (C.c_int, [_VP, C.c_int32, _VP, _PD, _PD]),

@@ -82,6 +82,62 @@ static T* dev_upload(const T* src, size_t count) {
   return p;
 }
 
+// ---- edge pairing: which leaf of the trajectory's other end rides with which row pass --------------------------
+// A NUTS trajectory grows at two ends, and the leapfrog states of each end are a sequence of their own.  While the tree works on
+// one end, a launch that streams X for a leaf (the REAL leaf) can evaluate the next not-yet-evaluated leapfrog of the other end
+// (a SHADOW leaf) on the same tiles; when the tree reaches that leaf, its launch starts from the parked wave sums instead of
+// streaming (a REPLAY).  Pure host logic: run_tree drives it, nuts_edge_pair_plan exposes it to the tests.
+//   * shadow leaves outstanding belong to ONE end at any time: a doubling first consumes what its own end holds (leaves
+//     0 .. n-1 are replays, which carry no shadow), only then do its streamed leaves evaluate ahead for the other end;
+//   * an end never holds more leaves than its next doubling has (`cap`: that doubling must be one the look-ahead knows the
+//     direction of), nor more than the ring; shadow leaf k is always leaf k of that doubling, so it is consumed in order.
+enum { EP_PLAIN = 0, EP_PAIRED = 1, EP_REPLAY = 2 };
+struct EdgePlan {
+  int ring = 64;
+  int side = 0, n = 0;      // outstanding shadow leaves: their end (+1 right, -1 left) and how many
+  unsigned head = 0;        // ring index of the oldest one
+  int cap = 0, used = 0;    // current doubling: leaves the OTHER end may hold (0: no pairing); replays it has consumed
+  int64_t ring_full = 0;    // leaves that streamed alone only because the ring had no room
+  void reset() { side = 0; n = 0; cap = 0; used = 0; }
+  // doubling d in direction `dir` is about to be queued; dir_of(e), d < e <= last: the directions the look-ahead may rely on
+  template <class F>
+  void begin(int d, int dir, int last, F dir_of) {
+    cap = 0; used = 0;
+    for (int e = d + 1; e <= last; ++e)
+      if (dir_of(e) == -dir) { cap = std::min(1 << std::min(e, 30), ring); break; }
+  }
+  // the next leaf of that doubling: what its launch is, the ring slot it reads / writes and the shadow leaf's index in its sequence
+  int leaf(int dir, int* slot, int* k) {
+    if (n > 0 && side == dir) { *slot = (int)(head % (unsigned)ring); *k = used++; ++head; --n; return EP_REPLAY; }
+    if (cap > 0 && n < cap) { side = -dir; *k = n; *slot = (int)((head + (unsigned)n) % (unsigned)ring); ++n; return EP_PAIRED; }
+    if (cap > 0 && n >= ring) ++ring_full;
+    *slot = -1; *k = -1;
+    return EP_PLAIN;
+  }
+};
+// The plan of a tree that runs doublings 0 .. n_doublings-1 in directions dirs[] (+1 / -1; n_dirs >= n_doublings of them are
+// known) under look-ahead depth `spec` and depth limit `max_depth`.  out[5 i ..]: {d, j, kind (0 plain, 1 paired, 2 replay),
+// ring slot or -1, index of the shadow / replayed leaf in its end's sequence or -1} of launch i.  Returns the number of launches.
+extern "C" int64_t nuts_edge_pair_plan(const int32_t* dirs, int32_t n_dirs, int32_t n_doublings, int32_t spec, int32_t max_depth,
+                                       int32_t ring, int32_t* out, int64_t out_cap) {
+  if (!dirs || !out || n_doublings < 0 || n_doublings > n_dirs || n_doublings > 20 || ring < 1) { g_err = "nuts_edge_pair_plan: bad argument"; return -1; }
+  EdgePlan ep;
+  ep.ring = ring;
+  int64_t n = 0;
+  const int last = std::min(std::min(spec, max_depth - 1), n_dirs - 1);
+  for (int d = 0; d < n_doublings; ++d) {
+    ep.begin(d, dirs[d], last, [&](int e) { return (int)dirs[e]; });
+    for (int j = 0; j < (1 << d); ++j, ++n) {
+      int slot, k;
+      const int kind = ep.leaf(dirs[d], &slot, &k);
+      if (n >= out_cap) { g_err = "nuts_edge_pair_plan: output too small"; return -1; }
+      int32_t* o = out + 5 * n;
+      o[0] = d; o[1] = j; o[2] = kind; o[3] = slot; o[4] = k;
+    }
+  }
+  return n;
+}
+
 #define PROF_RUN_MIN 16    // profiling: doublings of this many leaves or more are timed as ONE run of back-to-back launches
 #define SMALL_MAX_ELEMS 16384   // ... and the most factor elements it walks per gradient
 #define SMALL_MAX_N 1024  // largest model of the single-launch path (small_kernel.h: one thread per parameter, one workgroup)
@@ -128,6 +184,18 @@ struct nuts_model {
   int64_t orphan_elems = 0, factor_elems = 0;   // elements of the factors without an owning variable / of all factors (compile_spec)
   double rows_pack_s = 0.0;                  // host seconds the packed copy of the tiles cost when the model was built
   int64_t rows_xt_len = 0, rows_y_len = 0;   // group-aligned row pass: elements of the tiled X / y copies (chain groups compare them)
+  // edge pairing: the shadow sequence's records, block partials, local parts (its tickets: the second half of
+  // lg.ga_ticket) and the ring of parked wave sums; allocated when the model is eligible
+  int ep_ok = 0, ep_par = 0;
+  double *ep_ring = nullptr, *ep_part = nullptr, *ep_bpart = nullptr, *ep_def_loc = nullptr;
+  int64_t ep_ring_bytes = 0, ep_shadows = 0, ep_replays = 0;
+  int64_t ep_dropped = 0;     // shadow leaves no tree used: outstanding when their tree ended, or replayed only by a look-ahead doubling behind its end
+  int64_t ep_ring_full = 0;   // leaves that streamed alone only because the ring was full
+  int ep_turns = 0;           // most changes of direction between the doublings of one tree of depth >= 4 so far (tests)
+  struct EpLaunch {           // what the next group-aligned launch is (set by run_tree, consumed by launch_dense)
+    int kind = EP_PLAIN, slot = 0, sj = 0, sfold = 0, first = 0;
+    EvalIO sio{}; ArenaDev sA{};
+  } ep_launch;
   std::vector<LinDev> lins_host;   // linear predictors (dense node 5, lin_kernel.h) as uploaded by build_lins: launch_vector reads them per leapfrog
 
   template <typename T>
@@ -562,6 +630,34 @@ static void launch_dense(nuts_model* m, const ArenaDev& A, const EvalIO& io, int
       ga.fold = GA_FOLD_CTL | (job->src_prev ? GA_FOLD_SRC : 0);
       ga.cio = job->io; ga.cj = job->j; ga.cd = job->d; ga.cseq = job->seq;
     }
+    const nuts_model::EpLaunch ep = m->ep_launch;
+    m->ep_launch.kind = EP_PLAIN;
+    if (ep.kind == EP_PAIRED) {
+      // edge pairing: this leaf and the next leapfrog of the trajectory's other end in ONE pass over the (raw) tiles
+      GaMultiArgs<2, true> ma;
+      GaLeafArgs& L = ma.c[0];
+      L.A = A; L.io = io; L.cio = ga.cio; L.Emax = Emax; L.st = st;
+      L.ga_part = md.lg.ga_part; L.ga_bpart = md.lg.ga_bpart; L.ga_ticket = md.lg.ga_ticket; L.def_loc = md.def_loc;
+      L.j = j; L.fold = ga.fold; L.par = par; L.d = d; L.max_depth = max_depth; L.cj = ga.cj; L.cd = ga.cd; L.cseq = ga.cseq;
+      L.slot = 0; L.pad = 0;
+      GaLeafArgs& S = ma.c[1];
+      S.A = ep.sA; S.io = ep.sio; S.cio = ep.sio; S.Emax = Emax; S.st = nullptr;
+      S.ga_part = m->ep_part; S.ga_bpart = m->ep_bpart; S.ga_ticket = md.lg.ga_ticket + md.lg.ga_nblk; S.def_loc = m->ep_def_loc;
+      S.j = ep.sj; S.fold = ep.sfold; S.par = (m->ep_par ^= 1); S.d = 0; S.max_depth = 1; S.cj = 0; S.cd = 0; S.cseq = 0;
+      S.slot = GAM_MAXC - 1; S.pad = ep.first ? GAM_SH_FIRST : 0;   // (no control work: its fold never carries GA_FOLD_CTL)
+      ma.rev = rev; ma.pad = 0;
+      ma.ring = m->ep_ring + (size_t)ep.slot * md.lg.G * GA_RING_DOUBLES(8);
+      const dim3 pgrid(GAM_MAXC + md.lg.G);
+      if (md.lg.ga_dx == 7) hipLaunchKernelGGL((k_rows_ga_multi<2, 3, 7, true>), pgrid, block, 0, m->stream, md, ma);
+      else hipLaunchKernelGGL((k_rows_ga_multi<2, 3, 8, true>), pgrid, block, 0, m->stream, md, ma);
+      m->ep_shadows++;
+    } else if (ep.kind == EP_REPLAY) {
+      // ... and a leaf evaluated that way: the launch without its stream
+      const dim3 rgrid(m->rows_grid + (fold ? 1 : 0));
+      hipLaunchKernelGGL((k_rows_ga_replay<8>), rgrid, block, 0, m->stream, ga,
+                         (const double*)(m->ep_ring + (size_t)ep.slot * md.lg.G * GA_RING_DOUBLES(8)));
+      m->ep_replays++;
+    } else
     if (m->group && m->g_active && io.mode == MODE_TREE && m->group->kind >= 2) {
       // a member of a chain group inside a tree: the launch is deposited; the partner that completes the set submits ONE launch
       // that streams X once for all of them (rows_ga_multi_kernel.h)
@@ -1477,10 +1573,25 @@ static bool build_rows_group(nuts_model* m, const nuts_model_spec* s, const std:
   // (group-block pass: slot-major, every slot padded to a multiple of 64 records -- the padding stays zero)
   const size_t bpart_len = gpw ? 2 * (size_t)PART_STRIDE * ((lg.ga_nrec + WAVE - 1) / WAVE * WAVE) : 2 * (size_t)lg.ga_nrec * PART_STRIDE;
   lg.ga_bpart = m->keep(dev_alloc<double>(bpart_len));
-  lg.ga_ticket = m->keep(dev_alloc<unsigned>(lg.ga_nblk));
+  lg.ga_ticket = m->keep(dev_alloc<unsigned>(2 * (size_t)lg.ga_nblk));   // (second half: the shadow sequence's, edge pairing)
   if (lg.ga_part) hipMemset(lg.ga_part, 0, (size_t)lg.G * PART_STRIDE * sizeof(double));
   if (lg.ga_bpart) hipMemset(lg.ga_bpart, 0, bpart_len * sizeof(double));
-  if (lg.ga_ticket) hipMemset(lg.ga_ticket, 0, lg.ga_nblk * sizeof(unsigned));
+  if (lg.ga_ticket) hipMemset(lg.ga_ticket, 0, 2 * (size_t)lg.ga_nblk * sizeof(unsigned));
+  // ---- edge pairing: eligible is the single-chain group-aligned pass of the closed-form model (what k_rows_ga_multi evaluates) ----
+  m->ep_ok = 0;
+  if (!gpw && D == 8 && m->rows_rpl == 2 && m->ga_struct_ok == 1 && lg.ga_naux == 0 && env_int("NUTS_EDGE_PAIR", 1) != 0) {
+    const size_t ring_len = (size_t)GA_RING_LEAVES * lg.G * GA_RING_DOUBLES(8);
+    m->ep_ring = m->keep(dev_alloc<double>(ring_len));
+    m->ep_part = m->keep(dev_alloc<double>((size_t)lg.G * PART_STRIDE));
+    m->ep_bpart = m->keep(dev_alloc<double>(bpart_len));
+    m->ep_def_loc = m->keep(dev_alloc<double>(2 * 4 * (size_t)MAX_DEFERRED));
+    if (m->ep_ring && m->ep_part && m->ep_bpart && m->ep_def_loc) {
+      hipMemset(m->ep_part, 0, (size_t)lg.G * PART_STRIDE * sizeof(double));
+      hipMemset(m->ep_bpart, 0, bpart_len * sizeof(double));
+      hipMemset(m->ep_def_loc, 0, 2 * 4 * (size_t)MAX_DEFERRED * sizeof(double));
+      m->ep_ok = 1; m->ep_ring_bytes = (int64_t)(ring_len * sizeof(double));
+    } else (void)hipGetLastError();   // (a device that cannot hold the ring runs today's schedule)
+  }
   m->rows_grid = gpw ? lg.ga_nblk : lg.G;
   return true;
 }
@@ -2016,6 +2127,14 @@ extern "C" int nuts_model_get_scalar(const nuts_model* m, const char* name, doub
   // (a packed copy exists and the single-chain launch streams it; a chain group of this model runs k_rows_ga_multi on the raw tiles)
   else if (k == "rows_packed") *out = m->md.lg.ga ? m->md.lg.ga_pack : 0;
   else if (k == "rows_pack_build_s") *out = m->rows_pack_s;
+  // edge pairing: eligible and switched on; bytes of its ring; shadow leaves evaluated / leaves replayed so far
+  else if (k == "edge_pair") *out = m->ep_ok;
+  else if (k == "edge_pair_ring_bytes") *out = (double)m->ep_ring_bytes;
+  else if (k == "edge_pair_shadows") *out = (double)m->ep_shadows;
+  else if (k == "edge_pair_replays") *out = (double)m->ep_replays;
+  else if (k == "edge_pair_turns") *out = m->ep_turns;
+  else if (k == "edge_pair_dropped") *out = (double)m->ep_dropped;
+  else if (k == "edge_pair_ring_full") *out = (double)m->ep_ring_full;
   else if (k == "rows_aux_workgroups") *out = m->md.lg.ga ? m->md.lg.ga_naux : 0;
   else if (k == "mixture_workgroups") *out = m->md.has_mix ? m->md.mix.nwg : 0;
   else if (k == "glm_workgroups") *out = m->md.has_glm ? m->md.glm.nwg : 0;
@@ -2241,6 +2360,10 @@ struct nuts_chain {
   // leaf then also materialises the first half of that doubling's first leaf (EvalIO.pre_next 1 / 3), and `pre_done` tells the
   // first leaf of the next doubling that its k_leaf_pre launch is not needed
   int next_dir = 0; bool pre_done = false; int xpre = 1;
+  // edge pairing: on for this chain; the shadow sequence's two-slot arena view; the plan of the tree being built
+  bool edge_pair = false;
+  ArenaDev shA{};
+  EdgePlan ep;
   int spec_max = 10, last_depth = 0;   // look-ahead over the doublings, as deep as the previous tree went (run_tree)
   int pipe_draws = 1;                  // NUTS_PIPE_DRAWS, latched at creation: post-tuning draws of a batch are queued behind each other
   int logs_done = 0, logs_total = 0;  // logarithms of the pre-drawn uniforms taken / needed at most this draw
@@ -2417,7 +2540,7 @@ extern "C" nuts_chain* nuts_chain_create(nuts_model* m, const nuts_chain_config*
   c->wa_mean = c->keep(dev_alloc<double>(n)); c->wa_m2 = c->keep(dev_alloc<double>(n));
   c->wb_mean = c->keep(dev_alloc<double>(n)); c->wb_m2 = c->keep(dev_alloc<double>(n));
   A.var = c->var; A.inv_stds = c->inv_stds;
-  A.ga_ticket = m->md.lg.ga ? m->md.lg.ga_ticket : nullptr; A.ga_nticket = m->md.lg.ga ? m->md.lg.ga_nblk : 0;
+  A.ga_ticket = m->md.lg.ga ? m->md.lg.ga_ticket : nullptr; A.ga_nticket = m->md.lg.ga ? 2 * m->md.lg.ga_nblk : 0;
   if (c->full_adapt) {
     const size_t nn = (size_t)n * n;
     c->fa_initial_cov.assign(cfg->dense_cov, cfg->dense_cov + nn);
@@ -2444,6 +2567,17 @@ extern "C" nuts_chain* nuts_chain_create(nuts_model* m, const nuts_chain_config*
   c->fold_ctl = env_int("NUTS_FOLD_CTL", 1) != 0 && !(m->md.has_mvn && m->md.mv.winv);   // (the four-launch MvNormal pass has no workgroup 0 for it)
   c->spec_max = env_int("NUTS_SPEC_MAX", 10);
   c->xfold = env_int("NUTS_XFOLD", 1);
+  // edge pairing: the single-chain group-aligned pass without a host potential or a dense mass matrix, control folded across doublings
+  c->edge_pair = m->ep_ok && env_int("NUTS_EDGE_PAIR", 1) != 0 && !c->dense && !c->host_pot && !m->md.has_mvn && !m->explicit_pre &&
+                 m->md.lean_ok && c->fold_ctl && c->xfold;
+  if (c->edge_pair) {
+    c->shA = A;
+    c->shA.S = 2;
+    c->shA.Q = c->keep(dev_alloc<double>(2 * (size_t)n)); c->shA.P = c->keep(dev_alloc<double>(2 * (size_t)n));
+    c->shA.V = c->keep(dev_alloc<double>(2 * (size_t)n)); c->shA.G = c->keep(dev_alloc<double>(2 * (size_t)n));
+    if (!c->shA.Q || !c->shA.P || !c->shA.V || !c->shA.G) { (void)hipGetLastError(); c->edge_pair = false; }
+    c->ep.ring = std::max(1, std::min(GA_RING_LEAVES, env_int("NUTS_EDGE_PAIR_RING", GA_RING_LEAVES)));   // (a shorter ring: tests)
+  }
   c->pipe_draws = env_int("NUTS_PIPE_DRAWS", 1) != 0;
   c->xpre = env_int("NUTS_XPRE", 1);
   // NUTS_SMALL_LDS=0: the single-workgroup kernel with its tree in global memory, as before round 5 (A/B); NUTS_SMALL_LDS_SLOTS=k
@@ -3093,6 +3227,13 @@ static int run_tree(nuts_chain* c, const double* uniforms, double step_size, int
   };
   // (a host potential is called back leaf by leaf: nothing is queued ahead of a status it has not seen)
   const int spec = c->host_pot ? 0 : std::min(c->spec_max, c->last_depth - 1);
+  const bool pairing = c->edge_pair && !c->m->group && !c->host_pot && !c->dense;
+  int turns = 0;
+  int ep_replays_in[32] = {};   // replays queued per doubling
+  int prev_dir = 0;       // direction of the doubling queued before the one being queued (edge pairing)
+  bool ep_bad = false;
+  c->ep.reset();          // (shadow leaves a shorter tree left unused are dropped with their ring indices)
+  c->m->ep_launch.kind = EP_PLAIN;
   auto enqueue_doubling = [&](const Geometry& g, int d) {
     const int nleaf = 1 << d;
     ensure_logs(c, (2 << d) + d + 1);   // this doubling reads uniform indices < 2^(d+1) + d + 1
@@ -3101,7 +3242,32 @@ static int run_tree(nuts_chain* c, const double* uniforms, double step_size, int
     // this doubling's last control work with it.
     c->defer_last_ctl = c->xfold && c->fold_ctl && d + 1 < max_depth && d + 1 <= spec;
     c->next_dir = c->defer_last_ctl ? (uniforms[(2 << d) + d] < 0.5 ? 1 : -1) : 0;   // (the direction of doubling d + 1 whenever it is needed at all)
-    for (int j = 0; j < nleaf; ++j) enqueue_leaf(c, g, j, d, MODE_TREE, max_depth, j + 1 == nleaf ? seq : 0);
+    if (pairing) c->ep.begin(d, g.dir, std::min(spec, max_depth - 1), [&](int e) { return uniforms[(1 << e) + e - 1] < 0.5 ? 1 : -1; });
+    for (int j = 0; j < nleaf; ++j) {
+      if (pairing) {
+        // edge pairing: this leaf replays what was evaluated ahead, or takes the other end's next leapfrog with it
+        nuts_model::EpLaunch& el = c->m->ep_launch;
+        int k = 0;
+        el.kind = c->ep.leaf(g.dir, &el.slot, &k);
+        if (el.kind == EP_REPLAY) ++ep_replays_in[std::min(d, 31)];
+        if (el.kind == EP_REPLAY && k != j) { g_err = "internal error: edge pairing replays a leaf out of order"; ep_bad = true; el.kind = EP_PLAIN; }
+        if (el.kind == EP_PAIRED) {
+          const int od = -g.dir;
+          EvalIO sio{};
+          sio.mode = MODE_SIMPLE; sio.lean = 1;
+          sio.dir = od; sio.edge = od > 0 ? g.right : g.left; sio.left = g.left; sio.right = g.right;
+          sio.eps = od > 0 ? step_size : -step_size;
+          el.sio = sio; el.sj = k; el.sA = c->shA;
+          el.first = k == 0;
+          // its source: the previous shadow leaf (always the leaf of the shadow sequence's previous launch) -- or, for the first
+          // one, the other end's edge state in the chain's arena; that state is the leaf of the chain's previous launch exactly
+          // when this is the first launch after a doubling of the other end
+          el.sfold = k > 0 ? GA_FOLD_SRC : (j == 0 && d > 0 && prev_dir == od ? GA_FOLD_SRC : 0);
+        }
+      }
+      enqueue_leaf(c, g, j, d, MODE_TREE, max_depth, j + 1 == nleaf ? seq : 0);
+    }
+    prev_dir = g.dir;
     c->defer_last_ctl = false;
     return seq;
   };
@@ -3140,6 +3306,7 @@ static int run_tree(nuts_chain* c, const double* uniforms, double step_size, int
     if (flags & (ST_DIVERGING | ST_TURNING)) { exhausted = false; break; }
     if (d + 1 >= max_depth) break;
     const int dir = (flags & ST_DIR_POS) ? 1 : -1;
+    turns += dir != gm.dir;
     if (ahead_seq) {
       if (ahead.dir != dir) { g_err = "internal error: look-ahead mispredicted the direction of a doubling"; return NUTS_E_HIP; }
       gm = ahead; seq = ahead_seq;
@@ -3150,6 +3317,13 @@ static int run_tree(nuts_chain* c, const double* uniforms, double step_size, int
   }
   c->last_depth = depth_done;
   c->pend_valid = false;
+  if (depth_done >= 4) c->m->ep_turns = std::max(c->m->ep_turns, turns);
+  c->m->ep_ring_full = c->ep.ring_full;
+  if (pairing) {
+    c->m->ep_dropped += c->ep.n;
+    for (int d = depth_done; d < 32; ++d) c->m->ep_dropped += ep_replays_in[d];
+  }
+  if (ep_bad) return NUTS_E_HIP;
   *flags_out = flags;
   *exhausted_out = exhausted;
   return NUTS_OK;

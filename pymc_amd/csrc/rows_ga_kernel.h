@@ -293,6 +293,12 @@ __device__ __forceinline__ void ga_tile(const double (&x)[D][RPL], uint32_t yb, 
 #define GA_MAXW 4
 #define GA_MAXCHUNK 8      // the block reduce sums chunks of 8 consecutive groups (ga_bsz <= 64)
 #define GA_F_NOTAIL 1      // ga_flags, TIMING EXPERIMENTS ONLY: stop after the stream (results are wrong)
+// Edge pairing: a launch may evaluate, next to its own leaf, the next leapfrog of the trajectory's OTHER end on the
+// same tiles (rows_ga_multi_kernel.h, SH) and park that leaf's finished wave sums -- `s_acc`, all a tail needs from the stream --
+// in a ring entry of GA_RING_DOUBLES(D) doubles per group; when the tree reaches that leaf, `k_rows_ga_replay` below starts from
+// the entry instead of streaming X.
+#define GA_RING_LEAVES 64
+#define GA_RING_DOUBLES(D) (GA_MAXW * 2 * ((D) + 1))
 
 // Register budget: four waves per SIMD (128 VGPRs), two tiles in flight per wave.
 // G workgroups of W waves must all be resident: 16 waves per CU >= W (G / CUs).
@@ -735,4 +741,56 @@ __device__ __forceinline__ void ga_tail(const GaArgs& T, int g, double (&s_acc)[
   __syncthreads();
   if (!s_info[0]) return;
   ga_block_partial<D>(R, R.ga_part, R.ga_bpart, T.par, g, leaf, s_info, s_cp);
+}
+
+// A leaf whose wave sums were evaluated ahead (edge pairing): the launch of `k_rows_ga` without its stream.  No tile is requested;
+// the prologue is the one above on the same source state (only the tail wave needs its values: nobody forms beta_g), every
+// workgroup copies its ring entry into `s_acc`, and `ga_tail` runs as it stands -- the tree sees today's code on today's operands.
+// `ring`: this leaf's entry, [G][GA_MAXW][2][D + 1].  Models with auxiliary workgroups are not eligible (engine.hip).
+template <int D>
+__global__ __launch_bounds__(64 * GA_MAXW, 4) void k_rows_ga_replay(GaArgs a, const double* __restrict__ ring) {
+  const ModelDev& md = a.md;
+  const ArenaDev& A = a.A;
+  const EvalIO& io = a.io;
+  const int fold = a.fold, par = a.par;
+  const RowsDev& R = md.lg;
+  int b = (int)blockIdx.x;
+  if (fold & GA_FOLD_CTL) {   // workgroup 0: control work, from the previous launch's block partials
+    if (b == 0) { control_lean(md, A, a.cio, a.cj, a.cd, a.Emax, a.max_depth, a.st, a.cseq, lean_src(md, par ^ 1)); return; }
+    --b;
+  }
+  const int g = b;
+  if (g >= R.G) return;
+  const int tid = threadIdx.x, lane = tid & (WAVE - 1), w = __builtin_amdgcn_readfirstlane(tid >> 6);
+  Leaf lf; QView qv;
+  const int aborted = load_aborted(io, A);
+  resolve_leaf(io, A, a.j, lf, qv);
+  __shared__ double s_acc[GA_MAXW][2][D + 1];
+  __shared__ double s_red[NDOT];
+  __shared__ double s_cp[GA_MAXCHUNK][PART_STRIDE];
+  __shared__ int s_info[4];
+  __shared__ double s_keep[5][WAVE];
+  __shared__ __attribute__((aligned(16))) char s_args[(sizeof(GaArgs) + 15) / 16 * 16];
+  constexpr int NR = GA_RING_DOUBLES(D);
+  static_assert(NR <= 2 * WAVE, "two doubles of a ring entry per thread at most");
+  const double rv0 = ring[(int64_t)g * NR + min(tid, NR - 1)], rv1 = ring[(int64_t)g * NR + min(tid + WAVE, NR - 1)];   // (requested first)
+  {
+    const uint4* ka = (const uint4*)__builtin_amdgcn_kernarg_segment_ptr();
+    for (int t = tid; t < (int)((sizeof(GaArgs) + 15) / 16); t += (int)blockDim.x) reinterpret_cast<uint4*>(s_args)[t] = ka[t];
+  }
+  __syncthreads();   // (the copy is readable from here on)
+  if (w == 0) {
+    double hval0, hph0, zq, zph, m_lane, s_lane;
+    ga_hyper<D>(R, qv, fold, lean_src(md, par ^ 1), lane, hval0, hph0);
+    const int dl = lane % D;
+    ga_z_state(qv, R.off_z + g * D + dl, zq, zph);
+    ga_hyper_lanes<D>(R, hval0, dl, m_lane, s_lane);
+    s_keep[0][lane] = hval0; s_keep[1][lane] = hph0; s_keep[2][lane] = zq; s_keep[3][lane] = zph; s_keep[4][lane] = s_lane;
+  }
+  if (aborted) return;   // (no ticket, as a streamed leaf)
+  if (tid < WAVE) {   // (a workgroup has at least one wave)
+    (&s_acc[0][0][0])[tid] = rv0;
+    if (tid + WAVE < NR) (&s_acc[0][0][0])[tid + WAVE] = rv1;
+  }
+  ga_tail<D>(*reinterpret_cast<const GaArgs*>(s_args), g, s_acc, s_red, s_cp, s_info, s_keep);
 }

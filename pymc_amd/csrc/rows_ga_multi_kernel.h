@@ -40,10 +40,23 @@ struct GaLeafArgs {   // one chain's arguments of k_rows_ga (GaArgs without the 
   int slot, pad;         // the chain's place in its group: its control work always runs in workgroup `slot`
 };
 
-template <int NC>
+template <int NC, bool SH = false>
 struct GaMultiArgs {
   GaLeafArgs c[NC];
   int rev, pad;          // traversal order of a wave's two half-ranges in THIS launch (the result does not depend on it)
+};
+// SH (edge pairing; NC = 2): c[0] is the chain at a tree leaf, c[1] the SHADOW leaf -- the next leapfrog of the
+// trajectory's other end, a plain leapfrog chain (MODE_SIMPLE: no tree work, no control work) on buffers of its own: a two-slot
+// arena view, records, block partials, tickets, local parts.  `c[1].pad` bit 0: the shadow sequence starts here, its source
+// state is the other end's edge state in c[0]'s arena (with GA_FOLD_SRC: that state is the leaf of c[0]'s previous launch, so
+// mu' / sigma' come from c[0]'s block partials, as for a leaf of the chain itself).  The shadow leaf's finished wave sums go to
+// `ring`, this leaf's ring entry ([G][GA_MAXW][2][D + 1], rows_ga_kernel.h: k_rows_ga_replay picks them up).
+#define GAM_SH_FIRST 1
+template <int NC>
+struct GaMultiArgs<NC, true> {
+  GaLeafArgs c[NC];
+  int rev, pad;
+  double* ring;
 };
 
 __device__ __forceinline__ LeanSrc gam_src(const RowsDev& R, const GaLeafArgs& L, int par) {
@@ -65,9 +78,11 @@ __device__ __forceinline__ void gam_load(const double* base /* first element of 
 
 // D = 8 covariates, two rows per lane, two tile buffers per wave; DX stored columns (7: the intercept column is not stored).  Grid: GAM_MAXC control workgroups + G group workgroups; block: the W waves of the
 // model's layout (a wave's chunk of tiles is fixed when the model is created).
-template <int NC, int OCC, int DX>
-__global__ __launch_bounds__(64 * GA_MAXW, OCC) void k_rows_ga_multi(ModelDev md, GaMultiArgs<NC> ma) {
+template <int NC, int OCC, int DX, bool SH = false>
+__global__ __launch_bounds__(64 * GA_MAXW, OCC) void k_rows_ga_multi(ModelDev md, GaMultiArgs<NC, SH> ma) {
   constexpr int D = 8, RPL = 2, SPAN = WAVE * RPL, PIPE = 2;
+  static_assert(!SH || NC == 2, "edge pairing: the chain's leaf and one shadow leaf");
+  typedef GaMultiArgs<NC, SH> Args;
   typedef typename GaTileSel<DX>::type Tile;
   const RowsDev& R = md.lg;
   if ((int)blockIdx.x < GAM_MAXC) {   // control workgroups
@@ -88,7 +103,7 @@ __global__ __launch_bounds__(64 * GA_MAXW, OCC) void k_rows_ga_multi(ModelDev md
   __shared__ int s_info[NC][4];
   __shared__ double s_keep[NC][5][WAVE];            // the tail wave's per-lane prologue values of each chain
   __shared__ double s_beta[NC][D];                  // beta_g of each chain (written by the chain's wave, read by all into scalar registers)
-  __shared__ __attribute__((aligned(16))) char s_args[(sizeof(GaMultiArgs<NC>) + 15) / 16 * 16];
+  __shared__ __attribute__((aligned(16))) char s_args[(sizeof(Args) + 15) / 16 * 16];
 
   // ---- geometry of this wave's stream (as k_rows_ga) ----
   int T; int64_t ng, cbase;
@@ -115,9 +130,9 @@ __global__ __launch_bounds__(64 * GA_MAXW, OCC) void k_rows_ga_multi(ModelDev md
       for (int dd = 0; dd <= D; ++dd) { s_acc[c][w][0][dd] = 0.0; s_acc[c][w][1][dd] = 0.0; }
   }
   {   // the chains' arguments -> LDS: the tail reads them from there (nothing of them stays in scalar registers across the stream)
-    static_assert(alignof(GaMultiArgs<NC>) == 8 && sizeof(GaMultiArgs<NC>) % 8 == 0, "kernarg layout: the second argument follows the model at the next multiple of 8");
+    static_assert(alignof(Args) == 8 && sizeof(Args) % 8 == 0, "kernarg layout: the second argument follows the model at the next multiple of 8");
     const uint2* ka = (const uint2*)__builtin_amdgcn_kernarg_segment_ptr() + (sizeof(ModelDev) + 7) / 8;
-    for (int t = tid; t < (int)(sizeof(GaMultiArgs<NC>) / 8); t += (int)blockDim.x) reinterpret_cast<uint2*>(s_args)[t] = ka[t];
+    for (int t = tid; t < (int)(sizeof(Args) / 8); t += (int)blockDim.x) reinterpret_cast<uint2*>(s_args)[t] = ka[t];
   }
 
   // ---- prologue: chain c's by wave c mod W (the wave that will finish the chain): mu', sigma' of its leaf, z' of this group,
@@ -126,13 +141,19 @@ __global__ __launch_bounds__(64 * GA_MAXW, OCC) void k_rows_ga_multi(ModelDev md
   int dead = 0;
 #pragma unroll
   for (int c = 0; c < NC; ++c) dead |= load_aborted(ma.c[c].io, ma.c[c].A) ? (1 << c) : 0;
+  if constexpr (SH) dead = (dead & 1) ? 3 : 0;   // (the shadow leaf ends with the tree: no ticket on either set of counters)
   if (dead == (1 << NC) - 1) return;   // every chain's tree has ended: the launch drains (no tickets)
   for (int c = w; c < NC; c += W) {
     const GaLeafArgs& L = ma.c[c];
     Leaf lf; QView qv;
-    resolve_leaf(L.io, L.A, L.j, lf, qv);
     double hval0, hph0;
-    ga_hyper<D>(R, qv, L.fold, gam_src(R, L, L.par ^ 1), lane, hval0, hph0);
+    if (SH && c == 1 && (L.pad & GAM_SH_FIRST)) {   // the shadow sequence's first leaf: from the chain's arena (and block partials)
+      resolve_leaf(L.io, ma.c[0].A, L.j, lf, qv);
+      ga_hyper<D>(R, qv, L.fold, gam_src(R, ma.c[0], ma.c[0].par ^ 1), lane, hval0, hph0);
+    } else {
+      resolve_leaf(L.io, L.A, L.j, lf, qv);
+      ga_hyper<D>(R, qv, L.fold, gam_src(R, L, L.par ^ 1), lane, hval0, hph0);
+    }
     const int dl = lane % D;
     const int iz = R.off_z + g * D + dl;
     double zq, zph, m_lane, s_lane;
@@ -227,22 +248,31 @@ __global__ __launch_bounds__(64 * GA_MAXW, OCC) void k_rows_ga_multi(ModelDev md
   }
 
   // ---- tails: chain c is finished by wave c mod W; then the block partials of the chains this workgroup arrived last for ----
-  const GaMultiArgs<NC>& Tm = *reinterpret_cast<const GaMultiArgs<NC>*>(s_args);
+  const Args& Tm = *reinterpret_cast<const Args*>(s_args);
   MergePrefetch mpf;
   // (the operands of the first merge levels belong to earlier leaves: requested -- for the first chain a wave finishes -- before the
   // wave waits for the others)
-  if (w < NC && !((dead >> w) & 1)) {
+  if (w < NC && !((dead >> w) & 1) && !(SH && w == 1)) {
     const GaLeafArgs& L = Tm.c[w];
     Leaf lf; QView qv;
     resolve_leaf(L.io, L.A, L.j, lf, qv);
     merge_prefetch(L.A, lf, L.j, R.off_z + g * D + lane % D, mpf);
   }
   __syncthreads();
+  if constexpr (SH) {   // the shadow leaf's wave sums -> its ring entry (plain stores: the kernel boundary publishes them)
+    constexpr int NR = GA_RING_DOUBLES(D);
+    for (int t = tid; t < NR; t += (int)blockDim.x) Tm.ring[(int64_t)g * NR + t] = (&s_acc[1][0][0][0])[t];
+  }
   for (int c = w; c < NC; c += W) {
     if ((dead >> c) & 1) { if (lane == 0) s_info[c][0] = 0; continue; }
     const GaLeafArgs& L = Tm.c[c];
     Leaf lf; QView qv;
     resolve_leaf(L.io, L.A, L.j, lf, qv);
+    if (SH && c == 1) {   // (MODE_SIMPLE: the kick, q', the record, the ticket -- no leaf_post merges)
+      ga_tail_wave<D, false>(R, L.A, L.io, L.ga_part, L.ga_ticket, L.def_loc, lf, g, W, L.j, L.par, L.d, s_acc[c], s_red[c], s_info[c],
+                             s_keep[c][0][lane], s_keep[c][1][lane], s_keep[c][2][lane], s_keep[c][3][lane], s_keep[c][4][lane], nullptr);
+      continue;
+    }
     auto tail = [&](const MergePrefetch* pf) {   // (a compile-time pointer in either call: `mpf` stays in registers)
       ga_tail_wave<D, true>(R, L.A, L.io, L.ga_part, L.ga_ticket, L.def_loc, lf, g, W, L.j, L.par, L.d, s_acc[c], s_red[c], s_info[c],
                             s_keep[c][0][lane], s_keep[c][1][lane], s_keep[c][2][lane], s_keep[c][3][lane], s_keep[c][4][lane], pf);
