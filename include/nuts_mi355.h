@@ -320,8 +320,37 @@ int64_t nuts_model_algorithmic_bytes(const nuts_model *m);
  *                         "edge_pair_turns" the most changes of direction between the doublings of one tree of depth >= 4 so far,
  *                         "edge_pair_dropped" the leaves evaluated ahead for a doubling their tree never reached,
  *                         "edge_pair_ring_full" the leaves that streamed alone only because the ring had no room,
- *   "rows_waves", "lean", "single_workgroup_ok". */
+ *   "rows_waves", "lean", "single_workgroup_ok",
+ *   "loglik_batch"        draws per batch of nuts_model_loglik / nuts_waic_update; "loglik_stage_bytes" the bytes of the one
+ *                         [batch][N] block of pointwise values the model holds (0 before the first such call). */
 int nuts_model_get_scalar(const nuts_model *m, const char *name, double *out);
+
+/* ---- pointwise log-likelihood of a trace: `pm.compute_log_likelihood` (pymc/stats/log_density.py) and the per-observation
+ * reductions of `az.waic` ------------------------------------------------------------------------------------------------------
+ * What is evaluated: an OBSERVED element-wise factor (kind NUTS_LL_FACTOR, index = its place in nuts_model_spec.factors; any factor
+ * but a NUTS_D_DERIVED one is accepted -- which ones are observed is the caller's knowledge) or one of the dense nodes that are
+ * likelihoods by construction (logit rows, the mixture in MARGINAL form, the GLM; index ignored).  The value of element i at draw s
+ * is the term the joint log-density sums: support failures are -inf for that element, a failed PARAMETER check is -inf for every
+ * element of the factor at that draw (dist_math.py:50-74).  Logit rows come back in the spec's (group-sorted) row order.
+ * Draws are uploaded and evaluated in batches of nuts_model_get_scalar("loglik_batch"); the value of a draw does not depend on the
+ * batch it travelled in, bit for bit.  The calls use the model's own stream and are refused (NUTS_E_ARG, text in nuts_last_error())
+ * while the model is a member of a chain group, and for an index / node the model does not have. */
+enum { NUTS_LL_FACTOR = 0, NUTS_LL_LOGIT_ROWS = 1, NUTS_LL_MIXTURE = 2, NUTS_LL_GLM = 3 };
+int nuts_model_loglik_size(nuts_model *m, int32_t kind, int32_t index, int64_t *n);
+/* q: host [S][ndim], raveled UNCONSTRAINED draws (what the trace stores); out: host [S][N] */
+int nuts_model_loglik(nuts_model *m, int32_t kind, int32_t index, const double *q, int64_t S, double *out);
+/* Streaming WAIC: per observation (m, r, mean, M2) -- a running maximum with r = sum exp(ll - m) (an online logsumexp that stays
+ * finite while one draw's value is) and Welford's mean / M2 in draw order -- resident on the device and updated batch by batch; no
+ * [S][N] matrix exists anywhere.  The accumulators after draws fed in any split are bitwise those after one call.
+ *   nuts_waic_read:     lppd_i = log r + m - log S, p_waic_i = M2 / S (the population variance `az.waic` uses); either may be NULL
+ *   nuts_waic_read_raw: the four accumulator vectors [4][N]
+ * Destroy the handle before its model. */
+typedef struct nuts_waic nuts_waic;
+nuts_waic *nuts_waic_create(nuts_model *m, int32_t kind, int32_t index);
+int nuts_waic_update(nuts_waic *w, const double *q, int64_t S);
+int nuts_waic_read(nuts_waic *w, double *lppd_i, double *p_waic_i, int64_t *n_draws);
+int nuts_waic_read_raw(nuts_waic *w, double *acc);
+void nuts_waic_destroy(nuts_waic *w);
 
 /* ---- chain: replaces BaseHMC/NUTS + potential + step adaptation ------------- */
 /* NUTS_POT_FULL covers QuadPotentialFull and QuadPotentialFullInv (quadpotential.py:633-725): the caller passes

@@ -283,6 +283,13 @@ SYMBOLS = {
     "nuts_group_launches": (C.c_int, [_VP, C.POINTER(C.c_int64)]),
     "nuts_group_launches_wide": (C.c_int, [_VP, C.POINTER(C.c_int64), C.POINTER(C.c_int32)]),
     "nuts_unset_option": (C.c_int, [C.c_char_p]),
+    "nuts_model_loglik_size": (C.c_int, [_VP, C.c_int32, C.c_int32, C.POINTER(C.c_int64)]),
+    "nuts_model_loglik": (C.c_int, [_VP, C.c_int32, C.c_int32, _PD, C.c_int64, _PD]),
+    "nuts_waic_create": (_VP, [_VP, C.c_int32, C.c_int32]),
+    "nuts_waic_update": (C.c_int, [_VP, _PD, C.c_int64]),
+    "nuts_waic_read": (C.c_int, [_VP, _PD, _PD, C.POINTER(C.c_int64)]),
+    "nuts_waic_read_raw": (C.c_int, [_VP, _PD]),
+    "nuts_waic_destroy": (None, [_VP]),
 }
 
 _lib = None

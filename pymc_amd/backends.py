@@ -385,7 +385,7 @@ _STAT_RENAME = {"model_logp": "lp", "mean_tree_accept": "acceptance_rate", "dept
 
 
 def to_inference_dict(trace: MultiTrace, *, n_tune: int = 0, save_warmup: bool = False, include_transformed: bool = False,
-                      sampling_time: Optional[float] = None) -> Dict[str, Dict[str, np.ndarray]]:
+                      sampling_time: Optional[float] = None, log_likelihood: Optional[Dict[str, np.ndarray]] = None) -> Dict[str, Dict[str, np.ndarray]]:
     """What `pm.to_inference_data(trace)` puts into an `InferenceData` (`DataTreeConverter.posterior_to_xarray` /
     `sample_stats_to_xarray`, arviz.py:370-470) as a dict of groups of plain arrays -- ArviZ and xarray are not installable
     here, so the xarray wrapping is left to the caller (`arviz.from_dict(**groups)` takes exactly this):
@@ -395,6 +395,9 @@ def to_inference_dict(trace: MultiTrace, *, n_tune: int = 0, save_warmup: bool =
       sample_stats       {statistic: (chain, draw)}          the step method's statistics under ArviZ's names: model_logp -> lp,
                                                               mean_tree_accept -> acceptance_rate, depth -> tree_depth, tree_size -> n_steps
       warmup_posterior / warmup_sample_stats                  the first `n_tune` draws of every chain, with `save_warmup`
+      log_likelihood     {observed variable: (chain, draw, size)}  only when `log_likelihood` is given (`sample(log_likelihood=True)` or
+                                                              `pymc_amd.loglik.compute_log_likelihood`; arviz.py `log_likelihood_to_xarray`):
+                                                              the posterior draws' values, one (chain, draw) block per variable
       attrs              {"sampling_time", "tuning_steps"}
 
     `trace` holds tune + draws iterations per chain when it was sampled with `discard_tuned_samples=False`; `n_tune` says how many
@@ -415,5 +418,14 @@ def to_inference_dict(trace: MultiTrace, *, n_tune: int = 0, save_warmup: bool =
     if n_tune and save_warmup:
         out["warmup_posterior"], out["warmup_sample_stats"] = group(slice(0, n_tune))
     out["posterior"], out["sample_stats"] = group(slice(n_tune, None))
+    if log_likelihood is not None:
+        shape = next(iter(out["posterior"].values())).shape[:2] if out["posterior"] else None
+        grp = {}
+        for name, v in log_likelihood.items():
+            v = np.asarray(v)
+            if v.ndim < 2 or (shape is not None and v.shape[:2] != shape):
+                raise ValueError(f"log_likelihood[{name!r}] is {v.shape}: expected (chain, draw, ...) = {shape} + the variable's shape")
+            grp[name] = v
+        out["log_likelihood"] = grp
     out["attrs"] = {"sampling_time": sampling_time, "tuning_steps": n_tune}
     return out

@@ -24,6 +24,7 @@
 #include "kernels.h"
 #include "small_kernel.h"
 #include "mixture_kernel.h"
+#include "loglik_kernel.h"
 #include "nuts_mi355.h"
 #include "pcg64_stream.h"
 #include "advi.h"
@@ -197,6 +198,14 @@ struct nuts_model {
     EvalIO sio{}; ArenaDev sA{};
   } ep_launch;
   std::vector<LinDev> lins_host;   // linear predictors (dense node 5, lin_kernel.h) as uploaded by build_lins: launch_vector reads them per leapfrog
+  // pointwise log-likelihood (loglik_kernel.h): the factor table as the device holds it, and the buffers of ONE batch of LL_B draws,
+  // allocated when first asked for -- positions [LL_B][n], values [LL_B][ll_stage_n], the GLM node's Beta [LL_B][Ppad] and scalars
+  // [LL_B][4], the rows node's beta [LL_B][G][D], the draws with a failed parameter check [LL_B]
+  std::vector<nuts_factor> fac_host;
+  double *ll_q = nullptr, *ll_stage = nullptr, *ll_par = nullptr, *ll_sc = nullptr, *ll_lfact = nullptr;   // (ll_lfact: factln(y) per row of a Poisson GLM node)
+  int32_t* ll_dead = nullptr;
+  int64_t ll_stage_n = 0, ll_par_n = 0;
+  int n_waic = 0;                  // live nuts_waic handles on this model
 
   template <typename T>
   T* keep(T* p) {
@@ -505,21 +514,25 @@ static void launch_control_lean(nuts_model* m, const ArenaDev& A, const EvalIO& 
     hipLaunchKernelGGL(k_control_lean, dim3(1), dim3(VEC_THREADS), 0, m->stream, m->md, A, io, j, d, Emax, max_depth, st, seq, m->ga_par);
 }
 
+// linear predictors (lin_kernel.h): eta = X coef at this leaf's position, before the factors that read them are evaluated
+static void launch_lin_forward(nuts_model* m, const ArenaDev& A, const EvalIO& io, int j) {
+  const ModelDev& md = m->md;
+  if (md.n_lins <= 0) return;
+  if (md.n_derived > 0) hipLaunchKernelGGL(k_derive, dim3(2), dim3(256), 0, m->stream, md, A, io, j);   // (coefficients that are a derived vector)
+  for (int l = 0; l < md.n_lins; ++l) {
+    const LinDev& L = m->lins_host[l];
+    if (L.N == 1) { hipLaunchKernelGGL(k_lin_fwd1, dim3(L.K), dim3(1024), 0, m->stream, md, A, io, j, l); continue; }
+    const dim3 grid((unsigned)std::min<int64_t>(4096, (L.N + 255) / 256));
+    const size_t lds = (size_t)L.K * L.P * sizeof(double);
+#define LIN_FWD(KT) hipLaunchKernelGGL(k_lin_fwd<KT>, grid, dim3(256), lds, m->stream, md, A, io, j, l)
+    if (L.K == 1) LIN_FWD(1); else if (L.K == 2) LIN_FWD(2); else if (L.K <= 4) LIN_FWD(4); else if (L.K <= 8) LIN_FWD(8); else LIN_FWD(16);
+#undef LIN_FWD
+  }
+}
+
 static void launch_vector(nuts_model* m, const ArenaDev& A, const EvalIO& io, int j, int d) {
   const ModelDev& md = m->md;
-  // linear predictors (lin_kernel.h): eta = X coef at this leaf's position, before the factors that read them are swept
-  if (md.n_lins > 0) {
-    if (md.n_derived > 0) hipLaunchKernelGGL(k_derive, dim3(2), dim3(256), 0, m->stream, md, A, io, j);   // (coefficients that are a derived vector)
-    for (int l = 0; l < md.n_lins; ++l) {
-      const LinDev& L = m->lins_host[l];
-      if (L.N == 1) { hipLaunchKernelGGL(k_lin_fwd1, dim3(L.K), dim3(1024), 0, m->stream, md, A, io, j, l); continue; }
-      const dim3 grid((unsigned)std::min<int64_t>(4096, (L.N + 255) / 256));
-      const size_t lds = (size_t)L.K * L.P * sizeof(double);
-#define LIN_FWD(KT) hipLaunchKernelGGL(k_lin_fwd<KT>, grid, dim3(256), lds, m->stream, md, A, io, j, l)
-      if (L.K == 1) LIN_FWD(1); else if (L.K == 2) LIN_FWD(2); else if (L.K <= 4) LIN_FWD(4); else if (L.K <= 8) LIN_FWD(8); else LIN_FWD(16);
-#undef LIN_FWD
-    }
-  }
+  launch_lin_forward(m, A, io, j);   // ... before the factors that read the predictors are swept
   // gathered adjoints (model_dev.h GSlot): every element of the factors that read variables through index vectors is swept once,
   // before the kernels whose gathers add the results up (B and C below; the dense node's seed of a derived vector is already there)
   if (md.n_gsf > 0) {
@@ -1990,6 +2003,7 @@ static bool model_build(nuts_model* m, const nuts_model_spec* s) {
   if (md.fdead) hipMemset(md.fdead, 0, (size_t)std::max(s->n_factors, 1) * sizeof(int32_t));
   CompiledSpec cs;
   if (!compile_spec(m, s, cs)) return false;
+  m->fac_host = cs.fac;
   {   // the spec's data pool, then the engine's own vectors (derived values / seeds), zeroed
     double* pool = m->keep(dev_alloc<double>((size_t)std::max<int64_t>(s->data_pool_len + m->pool_extra, 1)));
     if (pool) {
@@ -2103,6 +2117,7 @@ extern "C" void nuts_model_destroy(nuts_model* m) {
   if (m->set_pin) hipHostFree(m->set_pin);
   if (m->group) group_remove_model(m->group, m);
   for (void* p : m->owned) if (p) hipFree(p);
+  for (void* p : {(void*)m->ll_q, (void*)m->ll_stage, (void*)m->ll_par, (void*)m->ll_sc, (void*)m->ll_dead, (void*)m->ll_lfact}) if (p) hipFree(p);
   for (auto e : m->ev) hipEventDestroy(e);
   if (m->host_pin) hipHostFree(m->host_pin);
   if (m->own_stream) hipStreamDestroy(m->own_stream);
@@ -2141,6 +2156,9 @@ extern "C" int nuts_model_get_scalar(const nuts_model* m, const char* name, doub
   else if (k == "glm_row_stride") *out = m->md.has_glm ? m->md.glm.xstride : 0;
   else if (k == "glm_layout_width") *out = m->md.has_glm ? m->md.glm.Ppad : 0;
   else if (k == "mvn_row_aligned") *out = m->md.has_mvn ? m->md.mv.aligned : 0;
+  // pointwise log-likelihood: draws per batch, and the bytes of the one [batch][N] block of values the model holds (0: never asked)
+  else if (k == "loglik_batch") *out = LL_B;
+  else if (k == "loglik_stage_bytes") *out = (double)(m->ll_stage_n * LL_B * (int64_t)sizeof(double));
   else if (k == "rows_waves") *out = m->md.lg.ga ? m->md.lg.ga_w : m->md.lg.n_waves;
   else if (k == "lean") *out = m->md.lean_ok;
   else if (k == "chain_group_kind") {   // what a chain group of this model's chains would merge: 0 nothing, 1 the MvNormal row-aligned pass, 2 the group-aligned row pass
@@ -2193,6 +2211,229 @@ extern "C" int nuts_model_logp_grad(nuts_model* m, const double* q, double* logp
   }
   if (grad) std::memcpy(grad, m->host_pin + n, n * sizeof(double));
   return NUTS_OK;
+}
+
+// ---- pointwise log-likelihood and streaming WAIC (loglik_kernel.h) --------------------------------------------------------------
+// What the calls are asked for: an observed factor (index = its place in the spec) or one of the three observed dense nodes.
+static int64_t ll_size(nuts_model* m, int kind, int index) {
+  const ModelDev& md = m->md;
+  switch (kind) {
+    case NUTS_LL_FACTOR:
+      if (index < 0 || index >= md.n_factors) { g_err = "log-likelihood: the index is not a factor of the model"; return -1; }
+      if (m->fac_host[index].dist == NUTS_D_DERIVED) { g_err = "log-likelihood: a derived vector has no log-density of its own"; return -1; }
+      return m->fac_host[index].size;
+    case NUTS_LL_LOGIT_ROWS: if (md.has_logit) return md.lg.N; break;
+    case NUTS_LL_MIXTURE:
+      if (md.has_mix && md.mix.assign) {
+        g_err = "log-likelihood: the conditional mixture's likelihood depends on assignments another step method rewrites per draw";
+        return -1;
+      }
+      if (md.has_mix) return md.mix.N;
+      break;
+    case NUTS_LL_GLM: if (md.has_glm) return md.glm.N; break;
+    default: g_err = "log-likelihood: unknown kind"; return -1;
+  }
+  g_err = "log-likelihood: the model has no such node";
+  return -1;
+}
+
+static int ll_check(nuts_model* m, int kind, int index, int64_t* N) {
+  if (!m) { g_err = "null argument"; return NUTS_E_ARG; }
+  if (m->group) { g_err = "log-likelihood: the model is a member of a chain group (its stream is the group's); remove the chain first"; return NUTS_E_ARG; }
+  const int64_t n = ll_size(m, kind, index);
+  if (n < 0) return NUTS_E_ARG;
+  *N = n;
+  return NUTS_OK;
+}
+
+// draws per batch: LL_B, or 1 under option NUTS_LL_B = 1 (the GLM kernel's own single-column instantiation: A/B in tools/loglik_bench.py)
+static int ll_batch() { return env_int("NUTS_LL_B", LL_B) == 1 ? 1 : LL_B; }
+
+static int ll_ensure(nuts_model* m, int kind, int64_t N) {
+  const ModelDev& md = m->md;
+  if (!m->ll_q) {
+    HIPCHK(hipMalloc((void**)&m->ll_q, (size_t)LL_B * std::max(md.n, 1) * sizeof(double)));
+    HIPCHK(hipMalloc((void**)&m->ll_dead, LL_B * sizeof(int32_t)));
+    HIPCHK(hipMalloc((void**)&m->ll_sc, 4 * LL_B * sizeof(double)));
+    HIPCHK(hipMemset(m->ll_sc, 0, 4 * LL_B * sizeof(double)));
+  }
+  if (m->ll_stage_n < N) {
+    HIPCHK(hipStreamSynchronize(m->stream));
+    if (m->ll_stage) hipFree(m->ll_stage);
+    m->ll_stage = nullptr; m->ll_stage_n = 0;
+    HIPCHK(hipMalloc((void**)&m->ll_stage, (size_t)LL_B * std::max<int64_t>(N, 1) * sizeof(double)));
+    m->ll_stage_n = N;
+  }
+  if (kind == NUTS_LL_GLM && md.glm.family == NUTS_GLM_POISSON && !m->ll_lfact) {
+    HIPCHK(hipMalloc((void**)&m->ll_lfact, (size_t)std::max<int64_t>(N, 1) * sizeof(double)));
+    hipLaunchKernelGGL(k_ll_factln, dim3((unsigned)((N + LL_BLOCK - 1) / LL_BLOCK)), dim3(LL_BLOCK), 0, m->stream, md.glm.y, N, m->ll_lfact);
+  }
+  const int64_t par = kind == NUTS_LL_GLM ? md.glm.Ppad : (kind == NUTS_LL_LOGIT_ROWS ? (int64_t)md.lg.G * md.lg.D : 0);
+  if (m->ll_par_n < par) {
+    HIPCHK(hipStreamSynchronize(m->stream));
+    if (m->ll_par) hipFree(m->ll_par);
+    m->ll_par = nullptr; m->ll_par_n = 0;
+    HIPCHK(hipMalloc((void**)&m->ll_par, (size_t)LL_B * par * sizeof(double)));
+    HIPCHK(hipMemset(m->ll_par, 0, (size_t)LL_B * par * sizeof(double)));   // (columns beyond a ragged batch are evaluated, never stored)
+    m->ll_par_n = par;
+  }
+  return NUTS_OK;
+}
+
+// the values of draws q[0 .. nb) (host, [nb][n]) into m->ll_stage [nb][N]; stream-ordered, no synchronisation
+static int ll_eval_batch(nuts_model* m, int kind, int index, const double* q, int nb, int64_t N, int B) {
+  const ModelDev& md = m->md;
+  const int n = md.n;
+  HIPCHK(hipMemcpyAsync(m->ll_q, q, (size_t)nb * n * sizeof(double), hipMemcpyHostToDevice, m->stream));
+  ArenaDev A{};
+  A.n = n; A.nblk = md.nblk; A.ept = m->ept; A.S = 1;
+  EvalIO io{};
+  io.mode = MODE_PLAIN; io.lean = md.lean_ok;
+  const unsigned nblk = (unsigned)((N + LL_BLOCK - 1) / LL_BLOCK);
+  if (kind == NUTS_LL_FACTOR) {
+    HIPCHK(hipMemsetAsync(m->ll_dead, 0, LL_B * sizeof(int32_t), m->stream));
+    if (md.n_lins > 0 || md.n_derived > 0) {
+      // the factor may read a predictor column or a derived vector: those are written per position by the model's own kernels
+      for (int b = 0; b < nb; ++b) {
+        io.q = m->ll_q + (size_t)b * n;
+        if (md.n_derived > 0 && md.n_lins == 0) hipLaunchKernelGGL(k_derive, dim3(2), dim3(256), 0, m->stream, md, A, io, 0);
+        launch_lin_forward(m, A, io, 0);
+        hipLaunchKernelGGL(k_ll_factor, dim3(nblk, 1), dim3(LL_BLOCK), 0, m->stream, md, io.q, index, m->ll_stage + (size_t)b * N, m->ll_dead + b);
+      }
+    } else
+      hipLaunchKernelGGL(k_ll_factor, dim3(nblk, nb), dim3(LL_BLOCK), 0, m->stream, md, (const double*)m->ll_q, index, m->ll_stage, m->ll_dead);
+    hipLaunchKernelGGL(k_ll_fill, dim3(nblk, nb), dim3(LL_BLOCK), 0, m->stream, m->ll_stage, N, (const int32_t*)m->ll_dead);
+  } else if (kind == NUTS_LL_GLM) {
+    const GlmDev& gm = md.glm;
+    if (gm.beta_buf) {
+      for (int b = 0; b < nb; ++b) {   // beta a derived vector: k_derive at this draw's position, then its column of Beta
+        io.q = m->ll_q + (size_t)b * n;
+        hipLaunchKernelGGL(k_derive, dim3(2), dim3(256), 0, m->stream, md, A, io, 0);
+        hipLaunchKernelGGL(k_ll_glm_prep, dim3(1), dim3(LL_BLOCK), 0, m->stream, md, io.q, b, m->ll_par, m->ll_sc);
+      }
+    } else
+      hipLaunchKernelGGL(k_ll_glm_prep, dim3(nb), dim3(LL_BLOCK), 0, m->stream, md, (const double*)m->ll_q, 0, m->ll_par, m->ll_sc);
+    const dim3 grid(gm.nwg), block(GLM_BLOCK);
+#define LLG(LL, CC) do { if (B == 1) hipLaunchKernelGGL((k_ll_glm<LL, CC, 1>), grid, block, 0, m->stream, gm, (const double*)m->ll_par, (const double*)m->ll_sc, nb, (const double*)m->ll_lfact, m->ll_stage); \
+                         else hipLaunchKernelGGL((k_ll_glm<LL, CC, LL_B>), grid, block, 0, m->stream, gm, (const double*)m->ll_par, (const double*)m->ll_sc, nb, (const double*)m->ll_lfact, m->ll_stage); } while (0)
+    switch (gm.lpr * 8 + gm.ch) {
+      case 1 * 8 + 1: LLG(1, 1); break;
+      case 1 * 8 + 2: LLG(1, 2); break;
+      case 1 * 8 + 4: LLG(1, 4); break;
+      case 2 * 8 + 4: LLG(2, 4); break;
+      case 4 * 8 + 4: LLG(4, 4); break;
+      case 8 * 8 + 4: LLG(8, 4); break;
+      case 16 * 8 + 4: LLG(16, 4); break;
+      case 32 * 8 + 3: LLG(32, 3); break;
+      case 32 * 8 + 4: LLG(32, 4); break;
+      case 64 * 8 + 3: LLG(64, 3); break;
+      default: LLG(64, 4); break;
+    }
+#undef LLG
+  } else if (kind == NUTS_LL_LOGIT_ROWS) {
+    const RowsDev& lg = md.lg;
+    const int64_t GD = (int64_t)lg.G * lg.D;
+    hipLaunchKernelGGL(k_ll_rows_beta, dim3((unsigned)((GD + LL_BLOCK - 1) / LL_BLOCK), nb), dim3(LL_BLOCK), 0, m->stream, md, (const double*)m->ll_q, m->ll_par);
+    hipLaunchKernelGGL(k_ll_rows, dim3(nblk, nb), dim3(LL_BLOCK), 0, m->stream, md, (const double*)m->ll_par, WAVE * m->rows_rpl,
+                       lg.ga_gpw ? 1 : lg.ga_w, m->ll_stage);
+  } else {
+    const dim3 grid(nblk, nb), block(MIX_BLOCK);
+    if (md.mix.K <= 4) hipLaunchKernelGGL(k_ll_mix<4>, grid, block, 0, m->stream, md, (const double*)m->ll_q, m->ll_stage);
+    else if (md.mix.K <= 8) hipLaunchKernelGGL(k_ll_mix<8>, grid, block, 0, m->stream, md, (const double*)m->ll_q, m->ll_stage);
+    else hipLaunchKernelGGL(k_ll_mix<16>, grid, block, 0, m->stream, md, (const double*)m->ll_q, m->ll_stage);
+  }
+  HIPCHK(hipGetLastError());
+  return NUTS_OK;
+}
+
+extern "C" int nuts_model_loglik_size(nuts_model* m, int32_t kind, int32_t index, int64_t* n) {
+  if (!n) { g_err = "null argument"; return NUTS_E_ARG; }
+  return ll_check(m, kind, index, n);
+}
+
+extern "C" int nuts_model_loglik(nuts_model* m, int32_t kind, int32_t index, const double* q, int64_t S, double* out) {
+  int64_t N = 0;
+  if (const int rc = ll_check(m, kind, index, &N)) return rc;
+  if (S < 0 || (S > 0 && (!q || !out))) { g_err = "null argument"; return NUTS_E_ARG; }
+  if (const int rc = ll_ensure(m, kind, N)) return rc;
+  const int B = ll_batch();
+  for (int64_t s0 = 0; s0 < S; s0 += B) {
+    const int nb = (int)std::min<int64_t>(B, S - s0);
+    if (const int rc = ll_eval_batch(m, kind, index, q + (size_t)s0 * m->md.n, nb, N, B)) return rc;
+    HIPCHK(hipMemcpyAsync(out + (size_t)s0 * N, m->ll_stage, (size_t)nb * N * sizeof(double), hipMemcpyDeviceToHost, m->stream));
+    HIPCHK(hipStreamSynchronize(m->stream));
+  }
+  HIPCHK(hipGetLastError());
+  return NUTS_OK;
+}
+
+struct nuts_waic {
+  nuts_model* m;
+  int32_t kind, index;
+  int64_t N, count;
+  double* acc;   // [4][N]: m, r, mean, M2
+};
+
+extern "C" nuts_waic* nuts_waic_create(nuts_model* m, int32_t kind, int32_t index) {
+  int64_t N = 0;
+  if (ll_check(m, kind, index, &N)) return nullptr;
+  auto* w = new nuts_waic{m, kind, index, N, 0, nullptr};
+  if (hipMalloc((void**)&w->acc, 4 * (size_t)std::max<int64_t>(N, 1) * sizeof(double)) != hipSuccess) {
+    g_err = "WAIC accumulators: device allocation failed"; delete w; return nullptr;
+  }
+  hipLaunchKernelGGL(k_waic_init, dim3((unsigned)((N + LL_BLOCK - 1) / LL_BLOCK + (N == 0))), dim3(LL_BLOCK), 0, m->stream, N, w->acc);
+  m->n_waic++;
+  return w;
+}
+
+extern "C" int nuts_waic_update(nuts_waic* w, const double* q, int64_t S) {
+  if (!w || S < 0 || (S > 0 && !q)) { g_err = "null argument"; return NUTS_E_ARG; }
+  nuts_model* m = w->m;
+  int64_t N = 0;
+  if (const int rc = ll_check(m, w->kind, w->index, &N)) return rc;
+  if (const int rc = ll_ensure(m, w->kind, N)) return rc;
+  const int B = ll_batch();
+  for (int64_t s0 = 0; s0 < S; s0 += B) {
+    const int nb = (int)std::min<int64_t>(B, S - s0);
+    if (const int rc = ll_eval_batch(m, w->kind, w->index, q + (size_t)s0 * m->md.n, nb, N, B)) return rc;
+    hipLaunchKernelGGL(k_waic_fold, dim3((unsigned)((N + LL_BLOCK - 1) / LL_BLOCK)), dim3(LL_BLOCK), 0, m->stream, (const double*)m->ll_stage, nb, N,
+                       w->count, w->acc);
+    w->count += nb;
+  }
+  HIPCHK(hipStreamSynchronize(m->stream));   // (the caller may reuse q)
+  HIPCHK(hipGetLastError());
+  return NUTS_OK;
+}
+
+extern "C" int nuts_waic_read(nuts_waic* w, double* lppd_i, double* p_waic_i, int64_t* n_draws) {
+  if (!w) { g_err = "null argument"; return NUTS_E_ARG; }
+  const int64_t N = w->N;
+  if (n_draws) *n_draws = w->count;
+  if (!lppd_i && !p_waic_i) return NUTS_OK;
+  std::vector<double> acc(4 * (size_t)std::max<int64_t>(N, 1));
+  HIPCHK(hipStreamSynchronize(w->m->stream));
+  HIPCHK(hipMemcpy(acc.data(), w->acc, 4 * (size_t)N * sizeof(double), hipMemcpyDeviceToHost));
+  const double S = (double)w->count;
+  for (int64_t i = 0; i < N; ++i) {
+    if (lppd_i) lppd_i[i] = std::log(acc[N + i]) + acc[i] - std::log(S);
+    if (p_waic_i) p_waic_i[i] = acc[3 * N + i] / S;
+  }
+  return NUTS_OK;
+}
+
+extern "C" int nuts_waic_read_raw(nuts_waic* w, double* acc /* [4][N] */) {
+  if (!w || !acc) { g_err = "null argument"; return NUTS_E_ARG; }
+  HIPCHK(hipStreamSynchronize(w->m->stream));
+  HIPCHK(hipMemcpy(acc, w->acc, 4 * (size_t)w->N * sizeof(double), hipMemcpyDeviceToHost));
+  return NUTS_OK;
+}
+
+extern "C" void nuts_waic_destroy(nuts_waic* w) {
+  if (!w) return;
+  hipStreamSynchronize(w->m->stream);
+  if (w->acc) hipFree(w->acc);
+  w->m->n_waic--;
+  delete w;
 }
 
 static void profile_enable(nuts_model* m, bool on, int sample_every, size_t max_pairs) {

@@ -1705,6 +1705,7 @@ class _Lowering:
                     if np.any(np.diff(g) < 0):
                         order = np.argsort(g, kind="stable")
                         X, g, observed = X[order], g[order], np.asarray(observed)[order]
+                        self.spec.rows_order = order
                     self.spec.logit_rows = ms.LogitRows(np.ascontiguousarray(X, dtype="float64"), np.ascontiguousarray(observed, dtype="int8"), g, km, ks, kz, "y")
                     return True
         return False
@@ -2480,13 +2481,22 @@ def lower_to_spec(model, vars=None) -> ms.ModelSpec:
     factors = model.logp(sum=False)
     owners = list(getattr(model, "logp_owners", [None] * len(factors)))
     names = list(getattr(model, "logp_names", [f"factor{i}" for i in range(len(factors))]))
+    # `model.logp_observed` (optional, aligned with the factors): which of them are observed RVs -- on a real `pm.Model`
+    # `[False] * len(free_RVs) + [True] * len(observed_RVs) + [False] * len(potentials)`; absent: none
+    observed = list(getattr(model, "logp_observed", [False] * len(factors)))
+    if len(observed) != len(factors):
+        raise ValueError(f"model.logp_observed has {len(observed)} entries for {len(factors)} factors of model.logp(sum=False)")
     memo: dict = {}
-    for g, own, nm in zip(factors, owners, names):
+    for g, own, nm, obs in zip(factors, owners, names, observed):
         try:
             tree = build_tree(g, memo)
         except NotLowerable:
             tree = None         # (only the shape-aware walk can express it -- slices of an expression: straight to the op-by-op lowering)
+        n_before = len(low.spec.factors)
         low.factor(tree, nm, own, graph=g)
+        if obs:     # (what the graph became: its own factor(s), not a derived vector it needed; a dense node is observed by construction)
+            for f in low.spec.factors[n_before:]:
+                f.observed = f.dist != ms.D_DERIVED
     # Categorical variables no conditional mixture claimed (`c ~ Categorical(w)` next to anything but `y ~ Normal(mu[c], ...)`): the
     # factor `log p[c]` is lowered op by op -- a selection among the K probabilities by the CURRENT value of c (`_select_chain`)
     for did in list(low._cat):

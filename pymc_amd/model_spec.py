@@ -167,6 +167,9 @@ class Factor:
     name: str = ""
     # expression program (include/nuts_mi355.h, "Expression programs"): what the arguments' OP_TMP operands refer to
     prog: Tuple[Instr, ...] = ()
+    # the factor is the likelihood of an OBSERVED variable (`pm.Normal(..., observed=y)`): its per-element log-density is what
+    # `pm.compute_log_likelihood` returns (pymc_amd/loglik.py)
+    observed: bool = False
 
 
 @dataclass
@@ -296,6 +299,9 @@ class ModelSpec:
     # data vectors [n_device_data:] are constants of the Deterministics only (masks, index vectors): the host evaluates those, the
     # device never reads them and they are not uploaded.  None: every vector is the device's
     n_device_data: Optional[int] = None
+    # logit rows: `rows_order[i]` = the caller's index of row i of `logit_rows` when the rows had to be sorted by group (None: they
+    # were passed sorted).  Pointwise results of the node are returned in the caller's order.
+    rows_order: Optional[np.ndarray] = None
 
     @property
     def n(self) -> int:
@@ -305,6 +311,24 @@ class ModelSpec:
     def point_map_info(self):
         """`RaveledVars.point_map_info` (pymc/blocking.py:40-46)."""
         return tuple((v.value_name, tuple(v.shape), v.size, np.dtype("float64")) for v in self.vars)
+
+
+# kinds of observed nodes (include/nuts_mi355.h NUTS_LL_*)
+LL_FACTOR, LL_LOGIT_ROWS, LL_MIXTURE, LL_GLM = 0, 1, 2, 3
+
+
+def observed_nodes(spec: "ModelSpec") -> List[Tuple[str, int, int, int]]:
+    """The observed variables of a spec as `(name, kind, index, size)`: the factors marked `observed` (kind LL_FACTOR, `index` =
+    the factor's place in `spec.factors`) and the dense nodes that are likelihoods by construction -- logit rows, the mixture over
+    observed rows, the GLM (index 0).  `mvnormal` is a prior."""
+    out = [(f.name, LL_FACTOR, i, int(f.size)) for i, f in enumerate(spec.factors) if getattr(f, "observed", False) and f.dist != D_DERIVED]
+    if spec.logit_rows is not None:
+        out.append((spec.logit_rows.name, LL_LOGIT_ROWS, 0, int(np.asarray(spec.logit_rows.y).size)))
+    if getattr(spec, "mixture_rows", None) is not None:
+        out.append((spec.mixture_rows.name, LL_MIXTURE, 0, int(np.asarray(spec.mixture_rows.y).size)))
+    if getattr(spec, "glm_rows", None) is not None:
+        out.append((spec.glm_rows.name, LL_GLM, 0, int(np.asarray(spec.glm_rows.y).size)))
+    return out
 
 
 # ---------------------------------------------------------------------------
@@ -774,7 +798,7 @@ class ModelBuilder:
                 val = Expr(self, Term(Operand(OP_DATA, 0.0, len(self.spec.data) - 1)), 1)
             size = max([val.size] + [p.size for p in params])
             terms, prog = self._lower_args([val, *params])
-            self.spec.factors.append(Factor(dist, size, terms, konst, name, prog))
+            self.spec.factors.append(Factor(dist, size, terms, konst, name, prog, observed=True))
             return None
         if shape is None:
             shape = ()
@@ -915,6 +939,7 @@ class ModelBuilder:
         if np.any(np.diff(g) < 0):
             order = np.argsort(g, kind="stable")
             X, g, y = X[order], g[order], np.asarray(y)[order]
+            self.spec.rows_order = order
         self.spec.logit_rows = LogitRows(
             X, np.ascontiguousarray(y, dtype="int8"), g, self._var_id(mu), self._var_id(sigma), self._var_id(z), name
         )

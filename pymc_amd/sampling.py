@@ -545,6 +545,7 @@ def sample(
     mp_ctx: Optional[str] = None,
     return_multitrace: bool = False,
     lockstep: Optional[bool] = None,
+    log_likelihood: bool = False,
     **step_kwargs,
 ):
     """Reduced `pm.sample` (mcmc.py:620-1190) returning raw arrays (and, with ``return_multitrace=True``, the reference's
@@ -577,11 +578,20 @@ def sample(
     chain, chain c on GPU c mod (visible devices) -- the reference's `cores > 1` layout (parallel.py:352-524) and the
     single-node way to use several GPUs without `torch.distributed`.  The step object is cloudpickled to the workers
     (`pymc_amd/parallel.py`); the result is the one sequential sampling gives.
+
+    ``log_likelihood`` (`pm.sample(idata_kwargs={"log_likelihood": True})`): after sampling, ``result["log_likelihood"]`` =
+    {observed variable: (chains, draws, size)} for the draws the result holds, evaluated on the device (pymc_amd/loglik.py).
     """
     rank, world, local = _dist_info()
     from pymc_amd.lowering import as_model_spec
 
     spec = model = as_model_spec(model)      # a ModelSpec, or a model object whose graphs are lowered here (`NotLowerable` otherwise)
+    if log_likelihood:
+        from pymc_amd.loglik import refusal
+
+        why = refusal(spec)
+        if why:
+            raise ValueError("log_likelihood=True refused: " + why)
     if device is None and world > 1:
         device = local
     # mcmc.py:907-908 -- every rank derives ALL chain generators so chain c is the same stream on any layout
@@ -830,6 +840,11 @@ def sample(
         from pymc_amd.backends import multitrace_from_result
 
         result["trace"] = multitrace_from_result(spec, result)
+    if log_likelihood:
+        from pymc_amd.loglik import compute_log_likelihood
+
+        f = getattr(step, "_logp_dlogp_func", None)
+        result["log_likelihood"] = compute_log_likelihood(spec, result["draws"], device=device, func=f if hasattr(f, "log_likelihood") else None)
     return result
 
 

@@ -222,6 +222,33 @@ class DeviceValueGradFunction:
             raise ValueError("Extra values are not set.")
         return {name: self._extra_vars_shared[name].copy() for name in self.spec.extra}
 
+    def _ll_node(self, name, node):
+        if node is not None:
+            return int(node[0]), int(node[1])
+        from pymc_amd.model_spec import observed_nodes
+
+        for nm, kind, index, _ in observed_nodes(self.spec):
+            if nm == name:
+                return kind, index
+        raise KeyError(f"{name!r} is not an observed variable of the model")
+
+    def log_likelihood(self, name: str, q, node=None) -> np.ndarray:
+        """Element-wise log-likelihood of observed variable `name` at the raveled unconstrained draws q [S, n] -> [S, size]
+        (`nuts_model_loglik`; logit rows in the spec's group-sorted order).  `node`: (kind, index) when the caller knows it."""
+        lib = _lib.load()
+        kind, index = self._ll_node(name, node)
+        q = np.ascontiguousarray(np.asarray(q, dtype="float64").reshape(-1, self.n))
+        size = C.c_int64()
+        _lib.check(lib.nuts_model_loglik_size(self._handle, kind, index, C.byref(size)), "nuts_model_loglik_size")
+        out = np.empty((q.shape[0], size.value))
+        _lib.check(lib.nuts_model_loglik(self._handle, kind, index, _lib.dptr(q), q.shape[0], _lib.dptr(out)), "nuts_model_loglik")
+        return out
+
+    def waic_accumulator(self, name: str, node=None) -> "WaicAccumulator":
+        """Device-resident per-observation WAIC accumulators of observed variable `name` (`nuts_waic_*`)."""
+        kind, index = self._ll_node(name, node)
+        return WaicAccumulator(self, kind, index)
+
     def time_kernels(self, q, reps=20):
         ms_tot, ms_dom = C.c_double(), C.c_double()
         q = np.ascontiguousarray(q, dtype="float64")
@@ -236,6 +263,51 @@ class DeviceValueGradFunction:
     def close(self):
         if getattr(self, "_handle", None):
             _lib.load().nuts_model_destroy(self._handle)
+            self._handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class WaicAccumulator:
+    """`nuts_waic`: (m, r, mean, M2) per observation, updated by any number of `update(q [S, n])` calls in any split."""
+
+    def __init__(self, func: DeviceValueGradFunction, kind: int, index: int):
+        lib = _lib.load()
+        self._func = func      # (the handle must not outlive its model)
+        size = C.c_int64()
+        _lib.check(lib.nuts_model_loglik_size(func._handle, kind, index, C.byref(size)), "nuts_model_loglik_size")
+        self.size = size.value
+        self._handle = lib.nuts_waic_create(func._handle, kind, index)
+        if not self._handle:
+            raise ValueError(f"nuts_waic_create: {_lib.last_error()}")
+
+    def update(self, q) -> None:
+        q = np.ascontiguousarray(np.asarray(q, dtype="float64").reshape(-1, self._func.n))
+        _lib.check(_lib.load().nuts_waic_update(self._handle, _lib.dptr(q), q.shape[0]), "nuts_waic_update")
+
+    def read(self):
+        """(lppd_i, p_waic_i, draws so far)"""
+        lppd, p = np.empty(self.size), np.empty(self.size)
+        n = C.c_int64()
+        _lib.check(_lib.load().nuts_waic_read(self._handle, _lib.dptr(lppd), _lib.dptr(p), C.byref(n)), "nuts_waic_read")
+        return lppd, p, n.value
+
+    def raw(self):
+        """(the accumulators [4, size]: m, r, mean, M2; draws so far)"""
+        acc = np.empty((4, self.size))
+        n = C.c_int64()
+        lib = _lib.load()
+        _lib.check(lib.nuts_waic_read_raw(self._handle, _lib.dptr(acc)), "nuts_waic_read_raw")
+        _lib.check(lib.nuts_waic_read(self._handle, None, None, C.byref(n)), "nuts_waic_read")
+        return acc, n.value
+
+    def close(self):
+        if getattr(self, "_handle", None):
+            _lib.load().nuts_waic_destroy(self._handle)
             self._handle = None
 
     def __del__(self):

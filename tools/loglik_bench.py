@@ -1,0 +1,112 @@
+"""Pointwise log-likelihood at the benchmark's shapes: what a draw costs, against one pass of the sampler's own kernel.
+
+    python tools/loglik_bench.py [--draws 64] [--out profiles/loglik_bench.json] [--small]
+
+At configs[3]'s GLM shape (1 M rows x 512 covariates, Bernoulli) and at C2-L (hierarchical-logit rows, 4 992 000 rows), on one GPU
+in one process:
+
+  * `nuts_model_loglik` for `--draws` draws in ONE call (device-synchronised wall time after a warm-up call; the [S][N] result
+    travels to the host, which is part of the call),
+  * `nuts_waic_update` for the same draws (the streaming accumulators: nothing but the draws crosses PCIe),
+  * the GLM kernel's own single-column instantiation (engine option NUTS_LL_B = 1) through the same `nuts_waic_update`,
+  * the PARENT's dominant pass at that shape: `DeviceValueGradFunction.time_kernels` (HIP events around the row-streaming kernel
+    of one logp + gradient).
+
+Reported per shape: microseconds per draw, the ratio to the parent's pass, and the bytes a draw moves by the shapes
+(GLM: 8 N P / B + 8 N; rows: 8 N per draw written, X read once per draw: 8 N D_stored + N).  The claim to check is "a batch of B
+draws costs about one read of X".  `--small` runs both shapes at 1/16 size (a smoke run of the tool itself).
+"""
+
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def _wall(fn, reps=1):
+    t0 = time.perf_counter()
+    for _ in range(reps):
+        fn()
+    return (time.perf_counter() - t0) / reps
+
+
+def measure(spec, name, draws, seed=0):
+    from pymc_amd import _lib
+    from pymc_amd.value_grad import DeviceValueGradFunction
+
+    f = DeviceValueGradFunction(spec, device=0)
+    q = np.random.default_rng(seed).normal(size=(draws, spec.n)) * 0.1
+    out = {}
+    try:
+        B = int(f.model_scalar("loglik_batch"))
+        ms_total, ms_dom = f.time_kernels(q[0], reps=20)
+        out["parent_pass_us"] = 1e3 * ms_dom
+        out["parent_logp_grad_us"] = 1e3 * ms_total
+        f.log_likelihood(name, q[:B])                     # warm-up: buffers, first launches
+        t = _wall(lambda: f.log_likelihood(name, q))
+        out["loglik_us_per_draw"] = 1e6 * t / draws
+
+        def waic_once():
+            acc = f.waic_accumulator(name)
+            acc.update(q)
+            acc.close()
+
+        waic_once()
+        out["waic_us_per_draw"] = 1e6 * _wall(waic_once, reps=3) / draws
+        if spec.glm_rows is not None:
+            _lib.set_engine_option("NUTS_LL_B", 1)
+            try:
+                waic_once()
+                out["waic_us_per_draw_B1"] = 1e6 * _wall(waic_once, reps=1) / draws
+            finally:
+                _lib.unset_engine_option("NUTS_LL_B")
+        out["batch"] = B
+        out["stage_bytes"] = int(f.model_scalar("loglik_stage_bytes"))
+    finally:
+        f.close()
+    for k in ("loglik_us_per_draw", "waic_us_per_draw", "waic_us_per_draw_B1"):
+        if k in out:
+            out[k.replace("_us_per_draw", "_over_parent_pass")] = out[k] / out["parent_pass_us"]
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--draws", type=int, default=64)
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "loglik_bench.json"))
+    ap.add_argument("--small", action="store_true")
+    a = ap.parse_args()
+    from pymc_amd import models
+
+    div = 16 if a.small else 1
+    res = {"draws": a.draws, "small": bool(a.small)}
+    N, P = 1_000_000 // div, 512
+    spec = models.glm_nuts(N=N, P=P, family="bernoulli")
+    r = measure(spec, "y", a.draws)
+    r.update(N=N, P=P, bytes_per_draw=8 * N * P / r["batch"] + 8 * N, bytes_parent_pass=8 * N * P)
+    res["glm"] = r
+    print(json.dumps({"glm": r}), flush=True)
+    del spec
+    G, D, rpg = 1248, 8, 4000 // div
+    spec = models.hier_logit(G=G, D=D, rows_per_group=rpg)
+    r = measure(spec, "y", a.draws)
+    Nr = G * rpg
+    r.update(N=Nr, D=D, bytes_per_draw=8 * Nr * (D - 1) + Nr + 8 * Nr, bytes_parent_pass=Nr * (8 * (D - 1) + 1))
+    res["c2l"] = r
+    print(json.dumps({"c2l": r}), flush=True)
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, "w") as fh:
+        json.dump(res, fh, indent=1, sort_keys=True)
+    print(json.dumps(res))
+
+
+if __name__ == "__main__":
+    main()
