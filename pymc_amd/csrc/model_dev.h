@@ -904,7 +904,10 @@ __device__ __forceinline__ void prog_op_adjoint(int op, double kconst, double g,
     case NUTS_E_ERF: gx = g * 1.1283791670955126 * exp(-x * x); px = true; break;
     case NUTS_E_ERFC: gx = -g * 1.1283791670955126 * exp(-x * x); px = true; break;
     case NUTS_E_ERFCX: gx = g * (2.0 * x * v - 1.1283791670955126); px = true; break;
-    case NUTS_E_LOG1MEXP: gx = -g / expm1(-x); px = true; break;
+    case NUTS_E_LOG1MEXP: {   // (at x = +-0 the quotient's sign is the sign of -x, as in the reference: the device library's expm1(-0.0) is +0.0)
+      const double u = expm1(-x);
+      gx = -g / (u == 0.0 ? -x : u); px = true;
+    } break;
     case NUTS_E_EXPM1: gx = g * (v + 1.0); px = true; break;
     case NUTS_E_MAXIMUM: case NUTS_E_MINIMUM: gx = g; gy = g; px = v == x; py = v == y; break;
     case NUTS_E_POW: gx = g * y * pow(x, y - 1.0); px = true; if (x != 0.0) { gy = g * v * log(x); py = true; } break;
