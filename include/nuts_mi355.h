@@ -351,6 +351,28 @@ int nuts_waic_update(nuts_waic *w, const double *q, int64_t S);
 int nuts_waic_read(nuts_waic *w, double *lppd_i, double *p_waic_i, int64_t *n_draws);
 int nuts_waic_read_raw(nuts_waic *w, double *acc);
 void nuts_waic_destroy(nuts_waic *w);
+/* Streaming PSIS-LOO (`az.loo`; Vehtari, Simpson, Gelman, Yao, Gabry, "Pareto smoothed importance sampling"): per observation the
+ * K1 = M + 1 smallest values of ll seen so far, M = ceil(min(S / 5, 3 sqrt(S / reff))) -- the tail of the importance ratios
+ * exp(-ll) and its cutoff -- as a sorted column keep[K1][N] (ascending, +inf where empty), and acc[4][N] = (m, r) of ll as
+ * nuts_waic keeps them, (m_rest, r_rest) the same running log-sum of -ll over every draw that is NOT kept.  Both stay on the device
+ * and are updated batch by batch; no [S][N] matrix exists anywhere.  The state after draws fed in any split is bitwise that after
+ * one call.  `n_draws` (>= 2) is fixed at creation because it sizes K1; `reff` is the relative efficiency of the draws (1.0: no
+ * correction).
+ *   nuts_psis_create:   NULL (text in nuts_last_error()) when K1 exceeds 1024 (about 116 000 draws at reff = 1), when the
+ *                       8 (K1 + 4) N bytes cannot be allocated, and where nuts_model_loglik refuses
+ *   nuts_psis_update:   NUTS_E_ARG past n_draws
+ *   nuts_psis_read:     fits the generalised Pareto distribution to each observation's tail and smooths it, on the device, once all
+ *                       n_draws are in (NUTS_E_ARG before): elpd_loo_i, the Pareto shape khat_i (+inf: a tail of 4 values or fewer)
+ *                       and lppd_i = log r + m - log S; any of them may be NULL.  An observation with ll = -inf at some draw has
+ *                       khat = +inf and elpd_loo_i = -inf; a NaN or +inf value gives NaN for both
+ *   nuts_psis_read_raw: keep [K1][N] and acc [4][N] as they stand (either may be NULL), K1
+ * Destroy the handle before its model. */
+typedef struct nuts_psis nuts_psis;
+nuts_psis *nuts_psis_create(nuts_model *m, int32_t kind, int32_t index, int64_t n_draws, double reff);
+int nuts_psis_update(nuts_psis *p, const double *q, int64_t S);
+int nuts_psis_read(nuts_psis *p, double *elpd_loo_i, double *khat_i, double *lppd_i, int64_t *n_draws);
+int nuts_psis_read_raw(nuts_psis *p, double *keep /* [K1][N] */, double *acc /* [4][N] */, int64_t *K1);
+void nuts_psis_destroy(nuts_psis *p);
 
 /* ---- chain: replaces BaseHMC/NUTS + potential + step adaptation ------------- */
 /* NUTS_POT_FULL covers QuadPotentialFull and QuadPotentialFullInv (quadpotential.py:633-725): the caller passes

@@ -290,6 +290,11 @@ SYMBOLS = {
     "nuts_waic_read": (C.c_int, [_VP, _PD, _PD, C.POINTER(C.c_int64)]),
     "nuts_waic_read_raw": (C.c_int, [_VP, _PD]),
     "nuts_waic_destroy": (None, [_VP]),
+    "nuts_psis_create": (_VP, [_VP, C.c_int32, C.c_int32, C.c_int64, C.c_double]),
+    "nuts_psis_update": (C.c_int, [_VP, _PD, C.c_int64]),
+    "nuts_psis_read": (C.c_int, [_VP, _PD, _PD, _PD, C.POINTER(C.c_int64)]),
+    "nuts_psis_read_raw": (C.c_int, [_VP, _PD, _PD, C.POINTER(C.c_int64)]),
+    "nuts_psis_destroy": (None, [_VP]),
 }
 
 _lib = None

@@ -205,7 +205,7 @@ struct nuts_model {
   double *ll_q = nullptr, *ll_stage = nullptr, *ll_par = nullptr, *ll_sc = nullptr, *ll_lfact = nullptr;   // (ll_lfact: factln(y) per row of a Poisson GLM node)
   int32_t* ll_dead = nullptr;
   int64_t ll_stage_n = 0, ll_par_n = 0;
-  int n_waic = 0;                  // live nuts_waic handles on this model
+  int n_waic = 0;                  // live nuts_waic / nuts_psis handles on this model
 
   template <typename T>
   T* keep(T* p) {
@@ -2434,6 +2434,105 @@ extern "C" void nuts_waic_destroy(nuts_waic* w) {
   if (w->acc) hipFree(w->acc);
   w->m->n_waic--;
   delete w;
+}
+
+// ---- streaming PSIS-LOO (psis.h, k_psis_fold / k_psis_finish) ----------------------------------------------------------------------
+struct nuts_psis {
+  nuts_model* m;
+  int32_t kind, index;
+  int64_t N, count, n_draws;
+  double reff;
+  int K1;
+  double *keep, *acc;   // [K1][N] ascending per column, +inf where empty; [4][N]: m, r of ll, m_rest, r_rest of -ll
+};
+
+extern "C" nuts_psis* nuts_psis_create(nuts_model* m, int32_t kind, int32_t index, int64_t n_draws, double reff) {
+  int64_t N = 0;
+  if (ll_check(m, kind, index, &N)) return nullptr;
+  if (n_draws < 2 || !(reff > 0.0) || !std::isfinite(reff)) { g_err = "PSIS: n_draws must be at least 2 and reff positive and finite"; return nullptr; }
+  const int64_t K1 = psis_tail_len(n_draws, reff) + 1;
+  if (K1 > PSIS_K1_MAX) {
+    g_err = "PSIS: the tail of " + std::to_string(n_draws) + " draws at reff " + std::to_string(reff) + " keeps " + std::to_string(K1) +
+            " values per observation, more than the cap of " + std::to_string(PSIS_K1_MAX);
+    return nullptr;
+  }
+  auto* p = new nuts_psis{m, kind, index, N, 0, n_draws, reff, (int)K1, nullptr, nullptr};
+  const size_t n1 = (size_t)std::max<int64_t>(N, 1);
+  if (hipMalloc((void**)&p->keep, (size_t)K1 * n1 * sizeof(double)) != hipSuccess || hipMalloc((void**)&p->acc, 4 * n1 * sizeof(double)) != hipSuccess) {
+    (void)hipGetLastError();
+    if (p->keep) hipFree(p->keep);
+    g_err = "PSIS state: device allocation of " + std::to_string((size_t)(K1 + 4) * n1 * sizeof(double)) + " bytes failed";
+    delete p; return nullptr;
+  }
+  hipLaunchKernelGGL(k_psis_init, dim3((unsigned)((N + LL_BLOCK - 1) / LL_BLOCK + (N == 0))), dim3(LL_BLOCK), 0, m->stream, N, (int)K1, p->keep, p->acc);
+  m->n_waic++;
+  return p;
+}
+
+extern "C" int nuts_psis_update(nuts_psis* p, const double* q, int64_t S) {
+  if (!p || S < 0 || (S > 0 && !q)) { g_err = "null argument"; return NUTS_E_ARG; }
+  nuts_model* m = p->m;
+  int64_t N = 0;
+  if (const int rc = ll_check(m, p->kind, p->index, &N)) return rc;
+  if (p->count + S > p->n_draws) {
+    g_err = "nuts_psis_update: " + std::to_string(p->count) + " + " + std::to_string(S) + " draws exceed the " + std::to_string(p->n_draws) +
+            " the handle was created for (they size its tail)";
+    return NUTS_E_ARG;
+  }
+  if (const int rc = ll_ensure(m, p->kind, N)) return rc;
+  const int B = ll_batch();
+  for (int64_t s0 = 0; s0 < S; s0 += B) {
+    const int nb = (int)std::min<int64_t>(B, S - s0);
+    if (const int rc = ll_eval_batch(m, p->kind, p->index, q + (size_t)s0 * m->md.n, nb, N, B)) return rc;
+    if (N > 0)
+      hipLaunchKernelGGL(k_psis_fold, dim3((unsigned)((N + LL_BLOCK - 1) / LL_BLOCK)), dim3(LL_BLOCK), 0, m->stream, (const double*)m->ll_stage, nb, N,
+                         p->K1, p->keep, p->acc);
+    p->count += nb;
+  }
+  HIPCHK(hipStreamSynchronize(m->stream));   // (the caller may reuse q)
+  HIPCHK(hipGetLastError());
+  return NUTS_OK;
+}
+
+extern "C" int nuts_psis_read(nuts_psis* p, double* elpd_loo_i, double* khat_i, double* lppd_i, int64_t* n_draws) {
+  if (!p) { g_err = "null argument"; return NUTS_E_ARG; }
+  if (n_draws) *n_draws = p->count;
+  if (!elpd_loo_i && !khat_i && !lppd_i) return NUTS_OK;
+  if (p->count != p->n_draws) {
+    g_err = "nuts_psis_read: " + std::to_string(p->count) + " of " + std::to_string(p->n_draws) + " draws are in (the tail is sized for all of them)";
+    return NUTS_E_ARG;
+  }
+  const int64_t N = p->N;
+  if (N == 0) return NUTS_OK;
+  double* out = nullptr;   // [3][N]: khat, elpd_loo_i, lppd_i
+  if (hipMalloc((void**)&out, 3 * (size_t)N * sizeof(double)) != hipSuccess) { (void)hipGetLastError(); g_err = "nuts_psis_read: device allocation failed"; return NUTS_E_HIP; }
+  hipLaunchKernelGGL(k_psis_finish, dim3((unsigned)((N + PSIS_FIN_BLOCK - 1) / PSIS_FIN_BLOCK)), dim3(PSIS_FIN_BLOCK), 0, p->m->stream,
+                     (const double*)p->keep, (const double*)p->acc, N, p->K1, p->n_draws, out);
+  hipError_t e = hipStreamSynchronize(p->m->stream);
+  if (e == hipSuccess && khat_i) e = hipMemcpy(khat_i, out, (size_t)N * sizeof(double), hipMemcpyDeviceToHost);
+  if (e == hipSuccess && elpd_loo_i) e = hipMemcpy(elpd_loo_i, out + N, (size_t)N * sizeof(double), hipMemcpyDeviceToHost);
+  if (e == hipSuccess && lppd_i) e = hipMemcpy(lppd_i, out + 2 * N, (size_t)N * sizeof(double), hipMemcpyDeviceToHost);
+  hipFree(out);
+  HIPCHK(e);
+  return NUTS_OK;
+}
+
+extern "C" int nuts_psis_read_raw(nuts_psis* p, double* keep /* [K1][N] */, double* acc /* [4][N] */, int64_t* K1) {
+  if (!p) { g_err = "null argument"; return NUTS_E_ARG; }
+  if (K1) *K1 = p->K1;
+  HIPCHK(hipStreamSynchronize(p->m->stream));
+  if (keep) HIPCHK(hipMemcpy(keep, p->keep, (size_t)p->K1 * (size_t)p->N * sizeof(double), hipMemcpyDeviceToHost));
+  if (acc) HIPCHK(hipMemcpy(acc, p->acc, 4 * (size_t)p->N * sizeof(double), hipMemcpyDeviceToHost));
+  return NUTS_OK;
+}
+
+extern "C" void nuts_psis_destroy(nuts_psis* p) {
+  if (!p) return;
+  hipStreamSynchronize(p->m->stream);
+  if (p->keep) hipFree(p->keep);
+  if (p->acc) hipFree(p->acc);
+  p->m->n_waic--;
+  delete p;
 }
 
 static void profile_enable(nuts_model* m, bool on, int sample_every, size_t max_pairs) {

@@ -20,9 +20,12 @@
 //                 (draw, row) reads its D columns from the model's resident copy of X in whichever layout it was built with.
 //   k_ll_mix      the marginal Normal mixture: a thread per (draw, row), the row's logsumexp over K <= 16 components.
 //   k_waic_fold   folds a [nb][N] block of values into the per-observation accumulators (m, r, mean, M2), draw by draw in draw order.
+//   k_psis_fold   folds the same block into the PSIS-LOO state of each observation (psis.h): its K1 smallest values and the running
+//                 log-sum of everything else; k_psis_finish fits and smooths each observation's tail once, at the end.
 #pragma once
 #include "kernels.h"
 #include "mixture_kernel.h"
+#include "psis.h"
 
 #define LL_B 8          // draws per batch (the GLM kernel's register budget decides: see DESIGN.md, pointwise log-likelihood)
 #define LL_BLOCK 256
@@ -244,4 +247,62 @@ __global__ __launch_bounds__(LL_BLOCK) void k_waic_init(int64_t N, double* __res
   const int64_t i = (int64_t)blockIdx.x * LL_BLOCK + threadIdx.x;
   if (i >= N) return;
   acc[i] = -INFINITY; acc[N + i] = 0.0; acc[2 * N + i] = 0.0; acc[3 * N + i] = 0.0;
+}
+
+// ---- f. PSIS-LOO state (psis.h) ------------------------------------------------------------------------------------------------
+// keep = [K1][N], rank-major (lane i and lane i + 1 touch neighbouring addresses), each column ascending in ll, +inf where empty;
+// acc = [4][N]: (m, r) of ll as k_waic_fold keeps them (lppd), (m_rest, r_rest) of -ll over what is not kept.  One thread per
+// observation folds its nb values in draw order.  A value not below the column's largest kept one (row K1 - 1: one coalesced
+// read) goes straight to the running pair; a wave in which no lane inserts touches nothing else.  In a wave that inserts, the
+// lanes walk the rank index j together from the bottom (psis_insert's loop runs while any lane still shifts), so every access to
+// row j is one row of neighbouring addresses.
+#define PSIS_FIN_BLOCK 64   // k_psis_finish: its candidates' work space, PSIS_WORK doubles per thread, is LDS
+__global__ __launch_bounds__(LL_BLOCK) void k_psis_fold(const double* __restrict__ ll, int nb, int64_t N, int K1, double* __restrict__ keep,
+                                                        double* __restrict__ acc) {
+  const int64_t i = (int64_t)blockIdx.x * LL_BLOCK + threadIdx.x;
+  if (i >= N) return;
+  double v[LL_B];
+#pragma unroll
+  for (int b = 0; b < LL_B; ++b) v[b] = b < nb ? ll[(int64_t)b * N + i] : 0.0;
+  double m = acc[i], r = acc[N + i], mr = acc[2 * N + i], rr = acc[3 * N + i];
+  double* col = keep + i;
+  double thr = col[(int64_t)(K1 - 1) * N];
+#pragma unroll
+  for (int b = 0; b < LL_B; ++b) {
+    if (b >= nb) break;
+    const double x = v[b];
+    if (x > m) { r = (m == -INFINITY ? 0.0 : r * exp(m - x)) + 1.0; m = x; }
+    else if (x > -INFINITY) r += exp(x - m);
+    else if (x != x) { r = x; }
+    const bool ins = x < thr;
+    if (!ins) psis_rest_fold(-x, mr, rr);
+    if (__any(ins)) {
+      if (ins) {
+        const double out = psis_insert(col, N, K1, x);
+        if (out != INFINITY) psis_rest_fold(-out, mr, rr);
+        thr = col[(int64_t)(K1 - 1) * N];
+      }
+    }
+  }
+  acc[i] = m; acc[N + i] = r; acc[2 * N + i] = mr; acc[3 * N + i] = rr;
+}
+
+__global__ __launch_bounds__(LL_BLOCK) void k_psis_init(int64_t N, int K1, double* __restrict__ keep, double* __restrict__ acc) {
+  const int64_t i = (int64_t)blockIdx.x * LL_BLOCK + threadIdx.x;
+  if (i >= N) return;
+  for (int j = 0; j < K1; ++j) keep[(int64_t)j * N + i] = INFINITY;
+  acc[i] = -INFINITY; acc[N + i] = 0.0; acc[2 * N + i] = -INFINITY; acc[3 * N + i] = 0.0;
+}
+
+// out = [3][N]: khat, elpd_loo_i, lppd_i = log r + m - log S.  The fit's candidates (b_j and the sums over the tail, m_est <= 61
+// of each) are a column of LDS per thread, [PSIS_WORK][PSIS_FIN_BLOCK]: lane l at 8 l bytes of a row, no bank is asked twice.
+__global__ __launch_bounds__(PSIS_FIN_BLOCK) void k_psis_finish(const double* __restrict__ keep, const double* __restrict__ acc, int64_t N,
+                                                               int K1, int64_t S, double* __restrict__ out) {
+  __shared__ double work[PSIS_WORK * PSIS_FIN_BLOCK];
+  const int64_t i = (int64_t)blockIdx.x * PSIS_FIN_BLOCK + threadIdx.x;
+  if (i >= N) return;
+  const PsisOut o = psis_finish(keep + i, N, K1, acc[2 * N + i], acc[3 * N + i], S, work + threadIdx.x, PSIS_FIN_BLOCK);
+  out[i] = o.khat;
+  out[N + i] = o.elpd;
+  out[2 * N + i] = log(acc[N + i]) + acc[i] - log((double)S);
 }

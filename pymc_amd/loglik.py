@@ -1,15 +1,17 @@
-"""Pointwise log-likelihood of a trace and streaming WAIC, on the device.
+"""Pointwise log-likelihood of a trace, streaming WAIC and streaming PSIS-LOO, on the device.
 
 `pm.compute_log_likelihood(idata)` (pymc/stats/log_density.py) evaluates the element-wise log-density of every observed variable at
 every draw; `az.waic` reduces that (chains x draws x observations) array per observation.  Here both run on the engine
 (csrc/loglik_kernel.h): `compute_log_likelihood` returns the arrays, `waic` accumulates the per-observation reductions on the device
-while the draws stream by and never holds the matrix -- the models this engine exists for have 10^6 observations.
+while the draws stream by and never holds the matrix -- the models this engine exists for have 10^6 observations.  `loo` (`az.loo`)
+does the same for Pareto-smoothed importance sampling (csrc/psis.h): per observation the tail of the importance ratios and one sum.
 
 The draws are what `sample()` returns: raveled, UNCONSTRAINED positions (chains, draws, n).
 """
 
 from __future__ import annotations
 
+import math
 from typing import Dict, List, Optional, Tuple
 
 import numpy as np
@@ -158,3 +160,65 @@ def waic(model, draws, *, var_name: Optional[str] = None, pointwise: bool = Fals
             f.close()
     a = caller_order(spec, node[1], a)
     return waic_from_accumulators(a[0], a[1], a[2], a[3], n_draws, pointwise=pointwise)
+
+
+def loo_from_pointwise(elpd_loo_i, khat_i, lppd_i, n_draws: int, pointwise: bool = False) -> dict:
+    """ArviZ's `loo` (log scale) from the per-observation results of PSIS over S = `n_draws` pooled draws: elpd_loo = sum elpd_loo_i,
+    p_loo = sum lppd_i - elpd_loo, se = sqrt(N var(elpd_loo_i)); `warning` when a Pareto shape exceeds good_k = min(1 - 1 / log10 S, 0.7)."""
+    elpd_i, khat, lppd_i = (np.asarray(a, dtype="float64") for a in (elpd_loo_i, khat_i, lppd_i))
+    N = elpd_i.size
+    good_k = min(1.0 - 1.0 / math.log10(float(n_draws)), 0.7)
+    with np.errstate(invalid="ignore"):
+        out = {
+            "elpd_loo": float(elpd_i.sum()),
+            "se": float(np.sqrt(N * np.var(elpd_i))),
+            "p_loo": float(lppd_i.sum() - elpd_i.sum()),
+            "n_samples": int(n_draws),
+            "n_data_points": int(N),
+            "warning": bool(np.any(khat > good_k)),
+            "good_k": float(good_k),
+        }
+    if pointwise:
+        out["loo_i"] = elpd_i
+        out["pareto_k"] = khat
+    return out
+
+
+def loo(model, draws, *, var_name: Optional[str] = None, pointwise: bool = False, reff: float = 1.0, device: Optional[int] = None,
+        func=None) -> dict:
+    """`az.loo(idata, var_name=...)` with the chains pooled in chain order: elpd_loo, se, p_loo, n_samples, n_data_points, warning,
+    good_k (and loo_i, pareto_k with `pointwise`), by Pareto-smoothed importance sampling from a state that stays on the device -- per
+    observation the tail of its importance ratios and one running sum; the (draws x observations) matrix is never formed.
+
+    `reff` is the relative efficiency of the draws (ArviZ's `reff` argument; 1.0: no correction).  ArviZ's own default estimates it
+    from the autocorrelation of exp(ll) per observation, which needs the whole matrix: that estimate is out of scope here, pass the
+    value if you have it."""
+    spec = _spec_of(model)
+    nodes = ms.observed_nodes(spec)
+    why = refusal(spec, [])
+    if why:
+        raise ValueError("log-likelihood refused: " + why)
+    if not nodes:
+        raise ValueError("the model has no observed variable")
+    if var_name is None and len(nodes) > 1:
+        raise TypeError(f"Found several log likelihood arrays {[nd[0] for nd in nodes]}, var_name cannot be None")
+    node = _select(spec, var_name)[0]
+    why = refusal(spec, [node])
+    if why:
+        raise ValueError("log-likelihood refused: " + why)
+    q = _draws_array(draws, spec.n)
+    n_draws = q.shape[0] * q.shape[1]
+    f, own = _function(spec, device, func)
+    try:
+        acc = f.psis_accumulator(node[0], n_draws, reff=reff, node=(node[1], node[2]))
+        try:
+            for c in range(q.shape[0]):
+                acc.update(q[c])
+            elpd_i, khat, lppd_i, _ = acc.read()
+        finally:
+            acc.close()
+    finally:
+        if own:
+            f.close()
+    elpd_i, khat, lppd_i = (caller_order(spec, node[1], a) for a in (elpd_i, khat, lppd_i))
+    return loo_from_pointwise(elpd_i, khat, lppd_i, n_draws, pointwise=pointwise)

@@ -249,6 +249,12 @@ class DeviceValueGradFunction:
         kind, index = self._ll_node(name, node)
         return WaicAccumulator(self, kind, index)
 
+    def psis_accumulator(self, name: str, n_draws: int, reff: float = 1.0, node=None) -> "PsisAccumulator":
+        """Device-resident per-observation PSIS-LOO state of observed variable `name` for a trace of `n_draws` pooled draws
+        (`nuts_psis_*`)."""
+        kind, index = self._ll_node(name, node)
+        return PsisAccumulator(self, kind, index, n_draws, reff)
+
     def time_kernels(self, q, reps=20):
         ms_tot, ms_dom = C.c_double(), C.c_double()
         q = np.ascontiguousarray(q, dtype="float64")
@@ -308,6 +314,54 @@ class WaicAccumulator:
     def close(self):
         if getattr(self, "_handle", None):
             _lib.load().nuts_waic_destroy(self._handle)
+            self._handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class PsisAccumulator:
+    """`nuts_psis`: per observation the tail of the importance ratios (the M + 1 smallest log-likelihood values) and the running
+    log-sum of the rest, updated by `update(q [S, n])` calls in any split until `n_draws` are in; `read()` then fits and smooths."""
+
+    def __init__(self, func: DeviceValueGradFunction, kind: int, index: int, n_draws: int, reff: float = 1.0):
+        lib = _lib.load()
+        self._func = func      # (the handle must not outlive its model)
+        size = C.c_int64()
+        _lib.check(lib.nuts_model_loglik_size(func._handle, kind, index, C.byref(size)), "nuts_model_loglik_size")
+        self.size = size.value
+        self.n_draws = int(n_draws)
+        self._handle = lib.nuts_psis_create(func._handle, kind, index, self.n_draws, float(reff))
+        if not self._handle:
+            raise ValueError(f"nuts_psis_create: {_lib.last_error()}")
+
+    def update(self, q) -> None:
+        q = np.ascontiguousarray(np.asarray(q, dtype="float64").reshape(-1, self._func.n))
+        _lib.check(_lib.load().nuts_psis_update(self._handle, _lib.dptr(q), q.shape[0]), "nuts_psis_update")
+
+    def read(self):
+        """(elpd_loo_i, khat_i, lppd_i, draws): only once all `n_draws` are in"""
+        elpd, khat, lppd = np.empty(self.size), np.empty(self.size), np.empty(self.size)
+        n = C.c_int64()
+        _lib.check(_lib.load().nuts_psis_read(self._handle, _lib.dptr(elpd), _lib.dptr(khat), _lib.dptr(lppd), C.byref(n)), "nuts_psis_read")
+        return elpd, khat, lppd, n.value
+
+    def raw(self):
+        """(keep [K1, size] ascending per column, +inf where empty; acc [4, size]: m, r of ll, m_rest, r_rest of -ll; draws so far)"""
+        lib = _lib.load()
+        k1, n = C.c_int64(), C.c_int64()
+        _lib.check(lib.nuts_psis_read_raw(self._handle, None, None, C.byref(k1)), "nuts_psis_read_raw")
+        keep, acc = np.empty((k1.value, self.size)), np.empty((4, self.size))
+        _lib.check(lib.nuts_psis_read_raw(self._handle, _lib.dptr(keep), _lib.dptr(acc), C.byref(k1)), "nuts_psis_read_raw")
+        _lib.check(lib.nuts_psis_read(self._handle, None, None, None, C.byref(n)), "nuts_psis_read")
+        return keep, acc, n.value
+
+    def close(self):
+        if getattr(self, "_handle", None):
+            _lib.load().nuts_psis_destroy(self._handle)
             self._handle = None
 
     def __del__(self):

@@ -1,6 +1,6 @@
 """Pointwise log-likelihood at the benchmark's shapes: what a draw costs, against one pass of the sampler's own kernel.
 
-    python tools/loglik_bench.py [--draws 64] [--out profiles/loglik_bench.json] [--small]
+    python tools/loglik_bench.py [--draws 64] [--loo-draws 1000] [--out profiles/loglik_bench.json] [--small]
 
 At configs[3]'s GLM shape (1 M rows x 512 covariates, Bernoulli) and at C2-L (hierarchical-logit rows, 4 992 000 rows), on one GPU
 in one process:
@@ -10,7 +10,11 @@ in one process:
   * `nuts_waic_update` for the same draws (the streaming accumulators: nothing but the draws crosses PCIe),
   * the GLM kernel's own single-column instantiation (engine option NUTS_LL_B = 1) through the same `nuts_waic_update`,
   * the PARENT's dominant pass at that shape: `DeviceValueGradFunction.time_kernels` (HIP events around the row-streaming kernel
-    of one logp + gradient).
+    of one logp + gradient),
+  * the LOO leg: `--loo-draws` draws around the initial point through `nuts_psis_update`, per draw over the whole trace and
+    separately over its first and last fifth (draws 0-199 and 800-999 of 1 000: the columns fill, against the steady state in
+    which most values are rejected at the threshold), `nuts_psis_read` once (k_psis_finish and the three result vectors to the
+    host), and `nuts_waic_update` over the same draws in the same run to stand next to it.
 
 Reported per shape: microseconds per draw, the ratio to the parent's pass, and the bytes a draw moves by the shapes
 (GLM: 8 N P / B + 8 N; rows: 8 N per draw written, X read once per draw: 8 N D_stored + N).  The claim to check is "a batch of B
@@ -38,7 +42,41 @@ def _wall(fn, reps=1):
     return (time.perf_counter() - t0) / reps
 
 
-def measure(spec, name, draws, seed=0):
+def measure_loo(f, name, n, draws, seed=1):
+    """The LOO leg on an open function: microseconds per draw of nuts_psis_update by phase, the finish, WAIC on the same draws."""
+    q = np.random.default_rng(seed).normal(size=(draws, n)) * 0.1
+    fifth = draws // 5
+    out = {"loo_draws": draws}
+
+    def waic_once():
+        acc = f.waic_accumulator(name)
+        acc.update(q)
+        acc.close()
+
+    out["loo_waic_us_per_draw"] = 1e6 * _wall(waic_once) / draws
+    acc = f.psis_accumulator(name, draws)
+    try:
+        t_fill = _wall(lambda: acc.update(q[:fifth]))
+        t_mid = _wall(lambda: acc.update(q[fifth:draws - fifth]))
+        t_steady = _wall(lambda: acc.update(q[draws - fifth:]))
+        out["psis_us_per_draw"] = 1e6 * (t_fill + t_mid + t_steady) / draws
+        out["psis_us_per_draw_fill"] = 1e6 * t_fill / fifth
+        out["psis_us_per_draw_steady"] = 1e6 * t_steady / fifth
+        t0 = time.perf_counter()
+        elpd, khat, lppd, _ = acc.read()
+        out["psis_read_ms"] = 1e3 * (time.perf_counter() - t0)
+        out["psis_K1"] = int(np.ceil(min(draws / 5.0, 3.0 * np.sqrt(draws)))) + 1
+        out["psis_state_bytes"] = 8 * (out["psis_K1"] + 4) * elpd.size
+        out["psis_khat_max"] = float(np.max(khat))
+        out["psis_elpd_loo"] = float(np.sum(elpd))
+    finally:
+        acc.close()
+    out["psis_steady_over_waic"] = out["psis_us_per_draw_steady"] / out["loo_waic_us_per_draw"]
+    out["psis_over_waic"] = out["psis_us_per_draw"] / out["loo_waic_us_per_draw"]
+    return out
+
+
+def measure(spec, name, draws, seed=0, loo_draws=0):
     from pymc_amd import _lib
     from pymc_amd.value_grad import DeviceValueGradFunction
 
@@ -70,6 +108,8 @@ def measure(spec, name, draws, seed=0):
                 _lib.unset_engine_option("NUTS_LL_B")
         out["batch"] = B
         out["stage_bytes"] = int(f.model_scalar("loglik_stage_bytes"))
+        if loo_draws:
+            out.update(measure_loo(f, name, spec.n, loo_draws))
     finally:
         f.close()
     for k in ("loglik_us_per_draw", "waic_us_per_draw", "waic_us_per_draw_B1"):
@@ -81,23 +121,24 @@ def measure(spec, name, draws, seed=0):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--draws", type=int, default=64)
+    ap.add_argument("--loo-draws", type=int, default=1000, help="draws of the LOO leg (0: skip it)")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "loglik_bench.json"))
     ap.add_argument("--small", action="store_true")
     a = ap.parse_args()
     from pymc_amd import models
 
     div = 16 if a.small else 1
-    res = {"draws": a.draws, "small": bool(a.small)}
+    res = {"draws": a.draws, "loo_draws": a.loo_draws, "small": bool(a.small)}
     N, P = 1_000_000 // div, 512
     spec = models.glm_nuts(N=N, P=P, family="bernoulli")
-    r = measure(spec, "y", a.draws)
+    r = measure(spec, "y", a.draws, loo_draws=a.loo_draws)
     r.update(N=N, P=P, bytes_per_draw=8 * N * P / r["batch"] + 8 * N, bytes_parent_pass=8 * N * P)
     res["glm"] = r
     print(json.dumps({"glm": r}), flush=True)
     del spec
     G, D, rpg = 1248, 8, 4000 // div
     spec = models.hier_logit(G=G, D=D, rows_per_group=rpg)
-    r = measure(spec, "y", a.draws)
+    r = measure(spec, "y", a.draws, loo_draws=a.loo_draws)
     Nr = G * rpg
     r.update(N=Nr, D=D, bytes_per_draw=8 * Nr * (D - 1) + Nr + 8 * Nr, bytes_parent_pass=Nr * (8 * (D - 1) + 1))
     res["c2l"] = r
