@@ -373,6 +373,33 @@ int nuts_psis_update(nuts_psis *p, const double *q, int64_t S);
 int nuts_psis_read(nuts_psis *p, double *elpd_loo_i, double *khat_i, double *lppd_i, int64_t *n_draws);
 int nuts_psis_read_raw(nuts_psis *p, double *keep /* [K1][N] */, double *acc /* [4][N] */, int64_t *K1);
 void nuts_psis_destroy(nuts_psis *p);
+/* Posterior predictive (`pm.sample_posterior_predictive`): one replicate y_rep of an observed node per draw, on the device, from a
+ * counter-based generator (pymc_amd/csrc/predictive.h: Philox4x32-10).  The value of (draw s, observation i) is a function of
+ * (seed, kind, index, s, i) and of the node's parameters at draw s, and of nothing else -- not of the batch, of the split of the
+ * draws over calls, of the kernel route or of the layout of X.  s is the GLOBAL draw number, draw0 + the position in the call; i is
+ * the index nuts_model_loglik uses (logit rows: the spec's group-sorted order).  Families: every NUTS_D_* but TRUNCNORMAL, BINOMIAL,
+ * POTENTIAL and DERIVED, the three GLM families, the logit rows, the marginal Normal mixture; the others are refused (NUTS_E_ARG,
+ * text in nuts_last_error()), as is whatever nuts_model_loglik refuses, an index above 16383 and a draw number of 2^32 or more.
+ * An element whose parameters are invalid (the parameter checks of the density) is NaN; a draw at which a NUTS_E_CHECK of the
+ * factor's program failed is NaN over its whole row.  Sizes are those of nuts_model_loglik_size.  All values are doubles.
+ * A factor whose argument 0 is not observed data (an expression of variables) is refused too: there is no vector to replicate.
+ *   nuts_model_predictive: q host [S][ndim] raveled UNCONSTRAINED draws, out host [S][N]
+ * Streaming checks (`az.plot_ppc`, `az.plot_bpv`): per observation Welford's (mean, M2) of y_rep and the counts #{y_rep < y_i},
+ * #{y_rep == y_i}; per draw T = (sum, sum of squares, min, max) of y_rep over the observations, from per-workgroup partials added in
+ * one fixed order.  Everything stays on the device and is updated batch by batch; no [S][N] matrix exists anywhere.  The state after
+ * draws fed in any split is bitwise that after one call.  Draws are numbered on from the handle's count.
+ * NaN replicates are not hidden: all four numbers of a draw that holds one are NaN (min and max propagate it as the sums do), and
+ * mean_i / var_i of an observation that met one stay NaN; its two counts, which a NaN never enters, are undefined there.
+ *   nuts_ppc_read:       mean_i, var_i = M2 / S, n_lt_i, n_eq_i (counts as doubles); any of them may be NULL
+ *   nuts_ppc_read_stats: T [n_draws][4] and T_obs [4], the same reduce over the observed data; either may be NULL
+ * Destroy the handle before its model. */
+int nuts_model_predictive(nuts_model *m, int32_t kind, int32_t index, const double *q, int64_t S, uint64_t seed, int64_t draw0, double *out);
+typedef struct nuts_ppc nuts_ppc;
+nuts_ppc *nuts_ppc_create(nuts_model *m, int32_t kind, int32_t index, uint64_t seed);
+int nuts_ppc_update(nuts_ppc *p, const double *q, int64_t S);
+int nuts_ppc_read(nuts_ppc *p, double *mean_i, double *var_i, double *n_lt_i, double *n_eq_i, int64_t *n_draws);
+int nuts_ppc_read_stats(nuts_ppc *p, double *T /* [n_draws][4] */, double *T_obs /* [4] */);
+void nuts_ppc_destroy(nuts_ppc *p);
 
 /* ---- chain: replaces BaseHMC/NUTS + potential + step adaptation ------------- */
 /* NUTS_POT_FULL covers QuadPotentialFull and QuadPotentialFullInv (quadpotential.py:633-725): the caller passes

@@ -25,6 +25,7 @@
 #include "small_kernel.h"
 #include "mixture_kernel.h"
 #include "loglik_kernel.h"
+#include "predictive_kernel.h"
 #include "nuts_mi355.h"
 #include "pcg64_stream.h"
 #include "advi.h"
@@ -205,7 +206,7 @@ struct nuts_model {
   double *ll_q = nullptr, *ll_stage = nullptr, *ll_par = nullptr, *ll_sc = nullptr, *ll_lfact = nullptr;   // (ll_lfact: factln(y) per row of a Poisson GLM node)
   int32_t* ll_dead = nullptr;
   int64_t ll_stage_n = 0, ll_par_n = 0;
-  int n_waic = 0;                  // live nuts_waic / nuts_psis handles on this model
+  int n_waic = 0;                  // live nuts_waic / nuts_psis / nuts_ppc handles on this model
 
   template <typename T>
   T* keep(T* p) {
@@ -2533,6 +2534,239 @@ extern "C" void nuts_psis_destroy(nuts_psis* p) {
   if (p->acc) hipFree(p->acc);
   p->m->n_waic--;
   delete p;
+}
+
+// ---- posterior predictive and its streaming checks (predictive.h, predictive_kernel.h) ----------------------------------------------
+// What nuts_model_loglik accepts, less the families predictive.h does not draw from; the node's tag of the counter
+static int pp_check(nuts_model* m, int kind, int index, int64_t* N, uint32_t* tag) {
+  if (const int rc = ll_check(m, kind, index, N)) return rc;
+  if (kind == NUTS_LL_FACTOR) {
+    const int dist = m->fac_host[index].dist;
+    const char* name = dist == NUTS_D_TRUNCNORMAL ? "TruncatedNormal" : dist == NUTS_D_BINOMIAL ? "Binomial" : dist == NUTS_D_POTENTIAL ? "Potential" : nullptr;
+    if (name || !pp_family_ok(dist)) {
+      g_err = std::string("posterior predictive: ") + (name ? name : "this family") + " is out of scope (no variate generator for it)";
+      return NUTS_E_ARG;
+    }
+    // argument 0 must be observed DATA: y_obs is read from it once, and a value that moves with the draw has nothing to replicate
+    const nuts_term& v = m->fac_host[index].arg[0];
+    for (const nuts_operand* o : {&v.a, &v.b, &v.c})
+      if (o->kind != NUTS_OP_CONST && o->kind != NUTS_OP_DATA) {
+        g_err = "posterior predictive: the factor's value is an expression of variables, not observed data";
+        return NUTS_E_ARG;
+      }
+  }
+  if (!pp_tag(kind, index, tag)) { g_err = "posterior predictive: the node's index does not fit the 14 bits the counter gives it"; return NUTS_E_ARG; }
+  return NUTS_OK;
+}
+
+static int pp_draw_range(int64_t draw0, int64_t S) {
+  if (draw0 < 0 || S < 0 || draw0 > ((int64_t)1 << 32) - S) { g_err = "posterior predictive: draw numbers must stay below 2^32"; return NUTS_E_ARG; }
+  return NUTS_OK;
+}
+
+// y_rep of draws q[0 .. nb) (host, [nb][n]), numbered s0 .. s0 + nb - 1, into m->ll_stage [nb][N]; stream-ordered, no synchronisation.
+// The routes are those of ll_eval_batch.
+static int pp_eval_batch(nuts_model* m, int kind, int index, const double* q, int nb, int64_t N, int B, PPAddr ad) {
+  const ModelDev& md = m->md;
+  const int n = md.n;
+  HIPCHK(hipMemcpyAsync(m->ll_q, q, (size_t)nb * n * sizeof(double), hipMemcpyHostToDevice, m->stream));
+  if (N == 0) return NUTS_OK;
+  ArenaDev A{};
+  A.n = n; A.nblk = md.nblk; A.ept = m->ept; A.S = 1;
+  EvalIO io{};
+  io.mode = MODE_PLAIN; io.lean = md.lean_ok;
+  const unsigned nblk = (unsigned)((N + LL_BLOCK - 1) / LL_BLOCK);
+  if (kind == NUTS_LL_FACTOR) {
+    HIPCHK(hipMemsetAsync(m->ll_dead, 0, LL_B * sizeof(int32_t), m->stream));
+    if (md.n_lins > 0 || md.n_derived > 0) {
+      for (int b = 0; b < nb; ++b) {
+        io.q = m->ll_q + (size_t)b * n;
+        if (md.n_derived > 0 && md.n_lins == 0) hipLaunchKernelGGL(k_derive, dim3(2), dim3(256), 0, m->stream, md, A, io, 0);
+        launch_lin_forward(m, A, io, 0);
+        PPAddr ab = ad;
+        ab.s0 += (uint32_t)b;
+        hipLaunchKernelGGL(k_pp_factor, dim3(nblk, 1), dim3(LL_BLOCK), 0, m->stream, md, io.q, index, m->ll_stage + (size_t)b * N, m->ll_dead + b, ab);
+      }
+    } else
+      hipLaunchKernelGGL(k_pp_factor, dim3(nblk, nb), dim3(LL_BLOCK), 0, m->stream, md, (const double*)m->ll_q, index, m->ll_stage, m->ll_dead, ad);
+    hipLaunchKernelGGL(k_pp_fill, dim3(nblk, nb), dim3(LL_BLOCK), 0, m->stream, m->ll_stage, N, (const int32_t*)m->ll_dead);
+  } else if (kind == NUTS_LL_GLM) {
+    const GlmDev& gm = md.glm;
+    if (gm.beta_buf) {
+      for (int b = 0; b < nb; ++b) {
+        io.q = m->ll_q + (size_t)b * n;
+        hipLaunchKernelGGL(k_derive, dim3(2), dim3(256), 0, m->stream, md, A, io, 0);
+        hipLaunchKernelGGL(k_ll_glm_prep, dim3(1), dim3(LL_BLOCK), 0, m->stream, md, io.q, b, m->ll_par, m->ll_sc);
+      }
+    } else
+      hipLaunchKernelGGL(k_ll_glm_prep, dim3(nb), dim3(LL_BLOCK), 0, m->stream, md, (const double*)m->ll_q, 0, m->ll_par, m->ll_sc);
+    const dim3 grid(gm.nwg), block(GLM_BLOCK);
+#define PPG(LL, CC) do { if (B == 1) hipLaunchKernelGGL((k_pp_glm<LL, CC, 1>), grid, block, 0, m->stream, gm, (const double*)m->ll_par, (const double*)m->ll_sc, nb, m->ll_stage); \
+                         else hipLaunchKernelGGL((k_pp_glm<LL, CC, LL_B>), grid, block, 0, m->stream, gm, (const double*)m->ll_par, (const double*)m->ll_sc, nb, m->ll_stage); } while (0)
+    switch (gm.lpr * 8 + gm.ch) {
+      case 1 * 8 + 1: PPG(1, 1); break;
+      case 1 * 8 + 2: PPG(1, 2); break;
+      case 1 * 8 + 4: PPG(1, 4); break;
+      case 2 * 8 + 4: PPG(2, 4); break;
+      case 4 * 8 + 4: PPG(4, 4); break;
+      case 8 * 8 + 4: PPG(8, 4); break;
+      case 16 * 8 + 4: PPG(16, 4); break;
+      case 32 * 8 + 3: PPG(32, 3); break;
+      case 32 * 8 + 4: PPG(32, 4); break;
+      case 64 * 8 + 3: PPG(64, 3); break;
+      default: PPG(64, 4); break;
+    }
+#undef PPG
+    const int dist = gm.family == NUTS_GLM_NORMAL ? NUTS_D_NORMAL : (gm.family == NUTS_GLM_BERNOULLI ? NUTS_D_BERNOULLI_LOGIT : NUTS_D_POISSON);
+    hipLaunchKernelGGL(k_pp_draw, dim3(nblk, nb), dim3(LL_BLOCK), 0, m->stream, m->ll_stage, N, dist, (const double*)m->ll_sc, ad);
+  } else if (kind == NUTS_LL_LOGIT_ROWS) {
+    const RowsDev& lg = md.lg;
+    const int64_t GD = (int64_t)lg.G * lg.D;
+    hipLaunchKernelGGL(k_ll_rows_beta, dim3((unsigned)((GD + LL_BLOCK - 1) / LL_BLOCK), nb), dim3(LL_BLOCK), 0, m->stream, md, (const double*)m->ll_q, m->ll_par);
+    hipLaunchKernelGGL(k_pp_rows, dim3(nblk, nb), dim3(LL_BLOCK), 0, m->stream, md, (const double*)m->ll_par, WAVE * m->rows_rpl,
+                       lg.ga_gpw ? 1 : lg.ga_w, m->ll_stage);
+    hipLaunchKernelGGL(k_pp_draw, dim3(nblk, nb), dim3(LL_BLOCK), 0, m->stream, m->ll_stage, N, (int)NUTS_D_BERNOULLI_LOGIT, (const double*)m->ll_sc, ad);
+  } else
+    hipLaunchKernelGGL(k_pp_mix, dim3(nblk, nb), dim3(MIX_BLOCK), 0, m->stream, md, (const double*)m->ll_q, m->ll_stage, ad);
+  HIPCHK(hipGetLastError());
+  return NUTS_OK;
+}
+
+extern "C" int nuts_model_predictive(nuts_model* m, int32_t kind, int32_t index, const double* q, int64_t S, uint64_t seed, int64_t draw0,
+                                     double* out) {
+  int64_t N = 0;
+  uint32_t tag = 0;
+  if (const int rc = pp_check(m, kind, index, &N, &tag)) return rc;
+  if (S < 0 || (S > 0 && (!q || !out))) { g_err = "null argument"; return NUTS_E_ARG; }
+  if (const int rc = pp_draw_range(draw0, S)) return rc;
+  if (const int rc = ll_ensure(m, kind, N)) return rc;
+  const int B = ll_batch();
+  for (int64_t s0 = 0; s0 < S; s0 += B) {
+    const int nb = (int)std::min<int64_t>(B, S - s0);
+    if (const int rc = pp_eval_batch(m, kind, index, q + (size_t)s0 * m->md.n, nb, N, B, PPAddr{pp_key(seed), tag, (uint32_t)(draw0 + s0)})) return rc;
+    HIPCHK(hipMemcpyAsync(out + (size_t)s0 * N, m->ll_stage, (size_t)nb * N * sizeof(double), hipMemcpyDeviceToHost, m->stream));
+    HIPCHK(hipStreamSynchronize(m->stream));
+  }
+  HIPCHK(hipGetLastError());
+  return NUTS_OK;
+}
+
+struct nuts_ppc {
+  nuts_model* m;
+  int32_t kind, index;
+  uint64_t seed;
+  uint32_t tag;
+  int64_t N, count, nblk, t_cap;
+  const double* y_obs;   // [N] in the node's evaluation order: the node's own vector, or y_own
+  double *y_own, *acc, *part, *T, *T_obs;   // acc [4][N]: mean, M2, n_lt, n_eq; part [nblk][LL_B][4]; T [t_cap][4]; T_obs [4]
+};
+
+static void ppc_free(nuts_ppc* p) {
+  for (double* d : {p->y_own, p->acc, p->part, p->T, p->T_obs}) if (d) hipFree(d);
+  delete p;
+}
+
+extern "C" nuts_ppc* nuts_ppc_create(nuts_model* m, int32_t kind, int32_t index, uint64_t seed) {
+  int64_t N = 0;
+  uint32_t tag = 0;
+  if (pp_check(m, kind, index, &N, &tag)) return nullptr;
+  if (ll_ensure(m, kind, N)) return nullptr;
+  auto* p = new nuts_ppc{m, kind, index, seed, tag, N, 0, (N + LL_BLOCK - 1) / LL_BLOCK, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  const size_t n1 = (size_t)std::max<int64_t>(N, 1), nb1 = (size_t)std::max<int64_t>(p->nblk, 1);
+  const bool own = kind == NUTS_LL_FACTOR || kind == NUTS_LL_LOGIT_ROWS;
+  if ((own && hipMalloc((void**)&p->y_own, n1 * sizeof(double)) != hipSuccess) || hipMalloc((void**)&p->acc, 4 * n1 * sizeof(double)) != hipSuccess ||
+      hipMalloc((void**)&p->part, nb1 * LL_B * 4 * sizeof(double)) != hipSuccess || hipMalloc((void**)&p->T_obs, 4 * sizeof(double)) != hipSuccess) {
+    (void)hipGetLastError();
+    g_err = "predictive checks: device allocation failed";
+    ppc_free(p);
+    return nullptr;
+  }
+  const ModelDev& md = m->md;
+  const unsigned nblk = (unsigned)p->nblk;
+  if (N > 0) {
+    if (kind == NUTS_LL_FACTOR) {
+      // argument 0 of an observed factor is data: the position it is evaluated at (zeros) does not enter it
+      hipMemsetAsync(m->ll_q, 0, (size_t)std::max(md.n, 1) * sizeof(double), m->stream);
+      hipLaunchKernelGGL(k_pp_factor_y, dim3(nblk), dim3(LL_BLOCK), 0, m->stream, md, (const double*)m->ll_q, index, p->y_own);
+    } else if (kind == NUTS_LL_LOGIT_ROWS)
+      hipLaunchKernelGGL(k_pp_rows_y, dim3(nblk, 1), dim3(LL_BLOCK), 0, m->stream, md, (const double*)m->ll_par, WAVE * m->rows_rpl,
+                         md.lg.ga_gpw ? 1 : md.lg.ga_w, p->y_own);
+    p->y_obs = own ? p->y_own : (kind == NUTS_LL_GLM ? md.glm.y : md.mix.y);
+    hipLaunchKernelGGL(k_ppc_init, dim3(nblk), dim3(LL_BLOCK), 0, m->stream, N, p->acc);
+    // T of the observed data: the same partials, the same reduce
+    hipLaunchKernelGGL(k_ppc_fold, dim3(nblk), dim3(LL_BLOCK), 0, m->stream, p->y_obs, 1, N, (int64_t)0, p->y_obs, (double*)nullptr, p->part);
+  }
+  hipLaunchKernelGGL(k_ppc_stats, dim3(1), dim3(LL_BLOCK), 0, m->stream, (const double*)p->part, p->nblk, p->T_obs);
+  if (hipStreamSynchronize(m->stream) != hipSuccess || hipGetLastError() != hipSuccess) {
+    g_err = "predictive checks: building y_obs failed";
+    ppc_free(p);
+    return nullptr;
+  }
+  m->n_waic++;
+  return p;
+}
+
+extern "C" int nuts_ppc_update(nuts_ppc* p, const double* q, int64_t S) {
+  if (!p || S < 0 || (S > 0 && !q)) { g_err = "null argument"; return NUTS_E_ARG; }
+  nuts_model* m = p->m;
+  int64_t N = 0;
+  uint32_t tag = 0;
+  if (const int rc = pp_check(m, p->kind, p->index, &N, &tag)) return rc;
+  if (const int rc = pp_draw_range(p->count, S)) return rc;
+  if (const int rc = ll_ensure(m, p->kind, N)) return rc;
+  if (p->count + S > p->t_cap) {   // T grows by doubling: the handle does not know the trace's length
+    const int64_t cap = std::max<int64_t>(std::max<int64_t>(2 * p->t_cap, p->count + S), 64);
+    double* T = nullptr;
+    HIPCHK(hipMalloc((void**)&T, (size_t)cap * 4 * sizeof(double)));
+    HIPCHK(hipStreamSynchronize(m->stream));
+    if (p->count > 0) HIPCHK(hipMemcpy(T, p->T, (size_t)p->count * 4 * sizeof(double), hipMemcpyDeviceToDevice));
+    if (p->T) hipFree(p->T);
+    p->T = T; p->t_cap = cap;
+  }
+  const int B = ll_batch();
+  for (int64_t s0 = 0; s0 < S; s0 += B) {
+    const int nb = (int)std::min<int64_t>(B, S - s0);
+    if (const int rc = pp_eval_batch(m, p->kind, p->index, q + (size_t)s0 * m->md.n, nb, N, B, PPAddr{pp_key(p->seed), tag, (uint32_t)p->count})) return rc;
+    if (N > 0)
+      hipLaunchKernelGGL(k_ppc_fold, dim3((unsigned)p->nblk), dim3(LL_BLOCK), 0, m->stream, (const double*)m->ll_stage, nb, N, p->count, p->y_obs,
+                         p->acc, p->part);
+    hipLaunchKernelGGL(k_ppc_stats, dim3(nb), dim3(LL_BLOCK), 0, m->stream, (const double*)p->part, p->nblk, p->T + 4 * p->count);
+    p->count += nb;
+  }
+  HIPCHK(hipStreamSynchronize(m->stream));   // (the caller may reuse q)
+  HIPCHK(hipGetLastError());
+  return NUTS_OK;
+}
+
+extern "C" int nuts_ppc_read(nuts_ppc* p, double* mean_i, double* var_i, double* n_lt_i, double* n_eq_i, int64_t* n_draws) {
+  if (!p) { g_err = "null argument"; return NUTS_E_ARG; }
+  if (n_draws) *n_draws = p->count;
+  const int64_t N = p->N;
+  if (N == 0 || (!mean_i && !var_i && !n_lt_i && !n_eq_i)) return NUTS_OK;
+  HIPCHK(hipStreamSynchronize(p->m->stream));
+  double* dst[4] = {mean_i, var_i, n_lt_i, n_eq_i};
+  for (int k = 0; k < 4; ++k)
+    if (dst[k]) HIPCHK(hipMemcpy(dst[k], p->acc + (size_t)k * N, (size_t)N * sizeof(double), hipMemcpyDeviceToHost));
+  if (var_i) {   // M2 / S, the population variance
+    const double S = (double)p->count;
+    for (int64_t i = 0; i < N; ++i) var_i[i] /= S;
+  }
+  return NUTS_OK;
+}
+
+extern "C" int nuts_ppc_read_stats(nuts_ppc* p, double* T, double* T_obs) {
+  if (!p) { g_err = "null argument"; return NUTS_E_ARG; }
+  HIPCHK(hipStreamSynchronize(p->m->stream));
+  if (T && p->count > 0) HIPCHK(hipMemcpy(T, p->T, (size_t)p->count * 4 * sizeof(double), hipMemcpyDeviceToHost));
+  if (T_obs) HIPCHK(hipMemcpy(T_obs, p->T_obs, 4 * sizeof(double), hipMemcpyDeviceToHost));
+  return NUTS_OK;
+}
+
+extern "C" void nuts_ppc_destroy(nuts_ppc* p) {
+  if (!p) return;
+  hipStreamSynchronize(p->m->stream);
+  p->m->n_waic--;
+  ppc_free(p);
 }
 
 static void profile_enable(nuts_model* m, bool on, int sample_every, size_t max_pairs) {

@@ -83,9 +83,10 @@ __global__ __launch_bounds__(LL_BLOCK) void k_ll_factln(const double* __restrict
   if (i < N) lf[i] = lgamma(y[i] + 1.0);
 }
 
-template <int LPR, int CH, int B>
-__global__ __launch_bounds__(GLM_BLOCK, 2) void k_ll_glm(GlmDev gm, const double* __restrict__ Beta, const double* __restrict__ sc, int nb,
-                                                        const double* __restrict__ lfact, double* __restrict__ out) {
+// The pass itself, shared with k_pp_glm (predictive_kernel.h): ETA = true stores the linear predictor instead of the row's value
+template <int LPR, int CH, int B, bool ETA>
+__device__ __forceinline__ void ll_glm_pass(const GlmDev& gm, const double* __restrict__ Beta, const double* __restrict__ sc, int nb,
+                                            const double* __restrict__ lfact, double* __restrict__ out) {
   const int FAMILY = gm.family;
   constexpr int RPW = WAVE / LPR;
   constexpr int NW = GLM_BLOCK / WAVE;
@@ -126,18 +127,29 @@ __global__ __launch_bounds__(GLM_BLOCK, 2) void k_ll_glm(GlmDev gm, const double
     request(r + RPW, xn, yn);   // unconditional (past the end it re-reads clamped rows): in flight during the arithmetic
     const bool first = r + grp < r1 && sub == 0;   // one lane per row stores the row's values
     const int64_t row = r + grp;
-    const double lf = lfact ? lfact[min(row, gm.N - 1)] : 0.0;   // Poisson: the row's own factln(y)
+    double lf = 0.0;
+    if constexpr (!ETA) lf = lfact ? lfact[min(row, gm.N - 1)] : 0.0;   // Poisson: the row's own factln(y)
 #pragma unroll
     for (int s = 0; s < B; ++s) {
       double part = 0.0;
 #pragma unroll
       for (int c = 0; c < CH; ++c) { part = fma(x[c].x, bb[s][c].x, part); part = fma(x[c].y, bb[s][c].y, part); }
       const double eta = glm_group_sum<LPR>(part) + icpt[s];
-      double lp, rr, ds;
-      glm_row(FAMILY, eta, y, sigma[s], inv_sigma[s], log_sigma[s], lp, rr, ds);
-      if (first && s < nb) out[(int64_t)s * gm.N + row] = lp - lf;
+      if constexpr (ETA) {
+        if (first && s < nb) out[(int64_t)s * gm.N + row] = eta;
+      } else {
+        double lp, rr, ds;
+        glm_row(FAMILY, eta, y, sigma[s], inv_sigma[s], log_sigma[s], lp, rr, ds);
+        if (first && s < nb) out[(int64_t)s * gm.N + row] = lp - lf;
+      }
     }
   }
+}
+
+template <int LPR, int CH, int B>
+__global__ __launch_bounds__(GLM_BLOCK, 2) void k_ll_glm(GlmDev gm, const double* __restrict__ Beta, const double* __restrict__ sc, int nb,
+                                                        const double* __restrict__ lfact, double* __restrict__ out) {
+  ll_glm_pass<LPR, CH, B, false>(gm, Beta, sc, nb, lfact, out);
 }
 
 // ---- c. hierarchical-logit rows ------------------------------------------------------------------------------------------------
@@ -153,7 +165,9 @@ __global__ __launch_bounds__(LL_BLOCK) void k_ll_rows_beta(ModelDev md, const do
 }
 
 // one thread per (draw, row in the spec's sorted order); LW: chunks per group of the per-group tile layout (build_rows_group)
-__global__ __launch_bounds__(LL_BLOCK) void k_ll_rows(ModelDev md, const double* __restrict__ beta, int span, int LW, double* __restrict__ out) {
+// (the body is shared with k_pp_rows, predictive_kernel.h: ETA = true stores the linear predictor; YOBS = true the row's y instead)
+template <bool ETA, bool YOBS>
+__device__ __forceinline__ void ll_rows_body(const ModelDev& md, const double* __restrict__ beta, int span, int LW, double* __restrict__ out) {
   const RowsDev& R = md.lg;
   const int64_t i = (int64_t)blockIdx.x * LL_BLOCK + threadIdx.x;
   const int b = blockIdx.y, D = R.D;
@@ -181,9 +195,16 @@ __global__ __launch_bounds__(LL_BLOCK) void k_ll_rows(ModelDev md, const double*
     for (int d = D - DX; d < D; ++d) eta = fma(x[(int64_t)(d - (D - DX)) * span], bg[d], eta);
     y = (double)R.y[base / DX + rr];
   }
-  double lp, rj;
-  logit_row(eta, y, lp, rj);
-  out[(int64_t)b * R.N + i] = lp;
+  if constexpr (YOBS) out[(int64_t)b * R.N + i] = y;
+  else if constexpr (ETA) out[(int64_t)b * R.N + i] = eta;
+  else {
+    double lp, rj;
+    logit_row(eta, y, lp, rj);
+    out[(int64_t)b * R.N + i] = lp;
+  }
+}
+__global__ __launch_bounds__(LL_BLOCK) void k_ll_rows(ModelDev md, const double* __restrict__ beta, int span, int LW, double* __restrict__ out) {
+  ll_rows_body<false, false>(md, beta, span, LW, out);
 }
 
 // ---- d. mixture node, marginal form --------------------------------------------------------------------------------------------

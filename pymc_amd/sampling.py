@@ -546,6 +546,7 @@ def sample(
     return_multitrace: bool = False,
     lockstep: Optional[bool] = None,
     log_likelihood: bool = False,
+    posterior_predictive: bool = False,
     **step_kwargs,
 ):
     """Reduced `pm.sample` (mcmc.py:620-1190) returning raw arrays (and, with ``return_multitrace=True``, the reference's
@@ -581,6 +582,12 @@ def sample(
 
     ``log_likelihood`` (`pm.sample(idata_kwargs={"log_likelihood": True})`): after sampling, ``result["log_likelihood"]`` =
     {observed variable: (chains, draws, size)} for the draws the result holds, evaluated on the device (pymc_amd/loglik.py).
+
+    ``posterior_predictive`` (`pm.sample_posterior_predictive` on the finished trace): ``result["posterior_predictive"]`` =
+    {observed variable: (chains, draws, size)}, one replicate per draw the result holds, drawn on the device
+    (pymc_amd/predictive.py) under the key `np.random.SeedSequence(random_seed).generate_state(1, np.uint64)[0]`; draw d of the model's
+    chain number c (``result["chains"]``: also where a rank holds only its own chains) is draw c * draws + d of the generator's stream.
+    ``random_seed=None`` takes a fresh key, in every process its own.  A model with an observed variable it cannot draw from is refused before sampling.
     """
     rank, world, local = _dist_info()
     from pymc_amd.lowering import as_model_spec
@@ -592,6 +599,12 @@ def sample(
         why = refusal(spec)
         if why:
             raise ValueError("log_likelihood=True refused: " + why)
+    if posterior_predictive:
+        from pymc_amd.predictive import refusal as pp_refusal
+
+        why = pp_refusal(spec)
+        if why:
+            raise ValueError("posterior_predictive=True refused: " + why)
     if device is None and world > 1:
         device = local
     # mcmc.py:907-908 -- every rank derives ALL chain generators so chain c is the same stream on any layout
@@ -845,6 +858,12 @@ def sample(
 
         f = getattr(step, "_logp_dlogp_func", None)
         result["log_likelihood"] = compute_log_likelihood(spec, result["draws"], device=device, func=f if hasattr(f, "log_likelihood") else None)
+    if posterior_predictive:
+        from pymc_amd.predictive import sample_posterior_predictive, seed_from
+
+        f = getattr(step, "_logp_dlogp_func", None)
+        result["posterior_predictive"] = sample_posterior_predictive(spec, result["draws"], random_seed=seed_from(random_seed), device=device, chain_ids=result["chains"],
+                                                                     func=f if hasattr(f, "posterior_predictive") else None)
     return result
 
 

@@ -255,6 +255,24 @@ class DeviceValueGradFunction:
         kind, index = self._ll_node(name, node)
         return PsisAccumulator(self, kind, index, n_draws, reff)
 
+    def posterior_predictive(self, name: str, q, seed: int = 0, draw0: int = 0, node=None) -> np.ndarray:
+        """One replicate of observed variable `name` per raveled unconstrained draw q [S, n] -> [S, size] (`nuts_model_predictive`;
+        logit rows in the spec's group-sorted order).  Draw s of the call is draw `draw0 + s` of the generator's stream under `seed`."""
+        lib = _lib.load()
+        kind, index = self._ll_node(name, node)
+        q = np.ascontiguousarray(np.asarray(q, dtype="float64").reshape(-1, self.n))
+        size = C.c_int64()
+        _lib.check(lib.nuts_model_loglik_size(self._handle, kind, index, C.byref(size)), "nuts_model_loglik_size")
+        out = np.empty((q.shape[0], size.value))
+        rc = lib.nuts_model_predictive(self._handle, kind, index, _lib.dptr(q), q.shape[0], int(seed) & 0xFFFFFFFFFFFFFFFF, int(draw0), _lib.dptr(out))
+        _lib.check(rc, "nuts_model_predictive")
+        return out
+
+    def ppc_accumulator(self, name: str, seed: int = 0, node=None) -> "PpcAccumulator":
+        """Device-resident streaming predictive checks of observed variable `name` (`nuts_ppc_*`)."""
+        kind, index = self._ll_node(name, node)
+        return PpcAccumulator(self, kind, index, seed)
+
     def time_kernels(self, q, reps=20):
         ms_tot, ms_dom = C.c_double(), C.c_double()
         q = np.ascontiguousarray(q, dtype="float64")
@@ -362,6 +380,54 @@ class PsisAccumulator:
     def close(self):
         if getattr(self, "_handle", None):
             _lib.load().nuts_psis_destroy(self._handle)
+            self._handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class PpcAccumulator:
+    """`nuts_ppc`: per observation (mean, M2) of the replicates and the counts below / at the observed value, per draw (sum, sum of
+    squares, min, max) over the observations, updated by any number of `update(q [S, n])` calls in any split; the draws are
+    numbered on from the handle's count."""
+
+    def __init__(self, func: DeviceValueGradFunction, kind: int, index: int, seed: int = 0):
+        lib = _lib.load()
+        self._func = func      # (the handle must not outlive its model)
+        size = C.c_int64()
+        _lib.check(lib.nuts_model_loglik_size(func._handle, kind, index, C.byref(size)), "nuts_model_loglik_size")
+        self.size = size.value
+        self._handle = lib.nuts_ppc_create(func._handle, kind, index, int(seed) & 0xFFFFFFFFFFFFFFFF)
+        if not self._handle:
+            raise ValueError(f"nuts_ppc_create: {_lib.last_error()}")
+
+    def update(self, q) -> None:
+        q = np.ascontiguousarray(np.asarray(q, dtype="float64").reshape(-1, self._func.n))
+        _lib.check(_lib.load().nuts_ppc_update(self._handle, _lib.dptr(q), q.shape[0]), "nuts_ppc_update")
+
+    def read(self):
+        """(mean_i, var_i = M2 / S, #{y_rep < y_i}, #{y_rep == y_i}, draws so far)"""
+        mean, var, n_lt, n_eq = (np.empty(self.size) for _ in range(4))
+        n = C.c_int64()
+        rc = _lib.load().nuts_ppc_read(self._handle, _lib.dptr(mean), _lib.dptr(var), _lib.dptr(n_lt), _lib.dptr(n_eq), C.byref(n))
+        _lib.check(rc, "nuts_ppc_read")
+        return mean, var, n_lt, n_eq, n.value
+
+    def stats(self):
+        """(T [draws, 4]: sum, sum of squares, min, max of each draw's replicate; T_obs [4]: the same of the observed data)"""
+        lib = _lib.load()
+        n = C.c_int64()
+        _lib.check(lib.nuts_ppc_read(self._handle, None, None, None, None, C.byref(n)), "nuts_ppc_read")
+        T, T_obs = np.empty((n.value, 4)), np.empty(4)
+        _lib.check(lib.nuts_ppc_read_stats(self._handle, _lib.dptr(T), _lib.dptr(T_obs)), "nuts_ppc_read_stats")
+        return T, T_obs
+
+    def close(self):
+        if getattr(self, "_handle", None):
+            _lib.load().nuts_ppc_destroy(self._handle)
             self._handle = None
 
     def __del__(self):

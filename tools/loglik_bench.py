@@ -1,6 +1,7 @@
 """Pointwise log-likelihood at the benchmark's shapes: what a draw costs, against one pass of the sampler's own kernel.
 
     python tools/loglik_bench.py [--draws 64] [--loo-draws 1000] [--out profiles/loglik_bench.json] [--small]
+    python tools/loglik_bench.py --predictive [--draws 64] [--out profiles/predictive_bench.json] [--small]
 
 At configs[3]'s GLM shape (1 M rows x 512 covariates, Bernoulli) and at C2-L (hierarchical-logit rows, 4 992 000 rows), on one GPU
 in one process:
@@ -15,6 +16,12 @@ in one process:
     separately over its first and last fifth (draws 0-199 and 800-999 of 1 000: the columns fill, against the steady state in
     which most values are rejected at the threshold), `nuts_psis_read` once (k_psis_finish and the three result vectors to the
     host), and `nuts_waic_update` over the same draws in the same run to stand next to it.
+
+`--predictive` runs the posterior-predictive leg INSTEAD (pymc_amd/predictive.py): microseconds per draw of `nuts_ppc_update` (the
+streaming checks: nothing but the draws crosses PCIe) and of `nuts_model_predictive` (the [S][N] replicates travel to the host),
+with `nuts_waic_update` over the same draws in the same run next to them, and their ratios to it.  By the shapes a draw of the
+predictive path moves what WAIC's moves (one read of X per batch of B) plus 16 N bytes: the row pass stores eta, k_pp_draw reads
+it and stores the variate in its place.
 
 Reported per shape: microseconds per draw, the ratio to the parent's pass, and the bytes a draw moves by the shapes
 (GLM: 8 N P / B + 8 N; rows: 8 N per draw written, X read once per draw: 8 N D_stored + N).  The claim to check is "a batch of B
@@ -76,6 +83,41 @@ def measure_loo(f, name, n, draws, seed=1):
     return out
 
 
+def measure_predictive(spec, name, draws, seed=0):
+    from pymc_amd.value_grad import DeviceValueGradFunction
+
+    f = DeviceValueGradFunction(spec, device=0)
+    q = np.random.default_rng(seed).normal(size=(draws, spec.n)) * 0.1
+    out = {}
+    try:
+        B = int(f.model_scalar("loglik_batch"))
+        _, ms_dom = f.time_kernels(q[0], reps=20)
+        out["parent_pass_us"] = 1e3 * ms_dom
+
+        def waic_once():
+            acc = f.waic_accumulator(name)
+            acc.update(q)
+            acc.close()
+
+        def ppc_once():
+            acc = f.ppc_accumulator(name, seed=1)
+            acc.update(q)
+            acc.close()
+
+        waic_once()
+        out["waic_us_per_draw"] = 1e6 * _wall(waic_once, reps=3) / draws
+        ppc_once()
+        out["ppc_us_per_draw"] = 1e6 * _wall(ppc_once, reps=3) / draws
+        f.posterior_predictive(name, q[:B], seed=1)
+        out["predictive_us_per_draw"] = 1e6 * _wall(lambda: f.posterior_predictive(name, q, seed=1)) / draws
+        out["batch"] = B
+    finally:
+        f.close()
+    out["ppc_over_waic"] = out["ppc_us_per_draw"] / out["waic_us_per_draw"]
+    out["predictive_over_waic"] = out["predictive_us_per_draw"] / out["waic_us_per_draw"]
+    return out
+
+
 def measure(spec, name, draws, seed=0, loo_draws=0):
     from pymc_amd import _lib
     from pymc_amd.value_grad import DeviceValueGradFunction
@@ -122,21 +164,38 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--draws", type=int, default=64)
     ap.add_argument("--loo-draws", type=int, default=1000, help="draws of the LOO leg (0: skip it)")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "loglik_bench.json"))
+    ap.add_argument("--out", default=None, help="default: profiles/loglik_bench.json (profiles/predictive_bench.json with --predictive)")
     ap.add_argument("--small", action="store_true")
+    ap.add_argument("--predictive", action="store_true", help="the posterior-predictive leg instead of the log-likelihood legs")
     a = ap.parse_args()
     from pymc_amd import models
 
+    a.out = a.out or os.path.join(ROOT, "profiles", "predictive_bench.json" if a.predictive else "loglik_bench.json")
     div = 16 if a.small else 1
     res = {"draws": a.draws, "loo_draws": a.loo_draws, "small": bool(a.small)}
     N, P = 1_000_000 // div, 512
+    G, D, rpg = 1248, 8, 4000 // div
+    if a.predictive:
+        res = {"draws": a.draws, "small": bool(a.small)}
+        r = measure_predictive(models.glm_nuts(N=N, P=P, family="bernoulli"), "y", a.draws)
+        r.update(N=N, P=P, bytes_per_draw_waic=8 * N * P / r["batch"] + 8 * N, bytes_per_draw_predictive=8 * N * P / r["batch"] + 8 * N + 16 * N)
+        res["glm"] = r
+        print(json.dumps({"glm": r}), flush=True)
+        Nr = G * rpg
+        r = measure_predictive(models.hier_logit(G=G, D=D, rows_per_group=rpg), "y", a.draws)
+        r.update(N=Nr, D=D, bytes_per_draw_waic=8 * Nr * (D - 1) + Nr + 8 * Nr, bytes_per_draw_predictive=8 * Nr * (D - 1) + Nr + 8 * Nr + 16 * Nr)
+        res["c2l"] = r
+        print(json.dumps({"c2l": r}), flush=True)
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as fh:
+            json.dump(res, fh, indent=1, sort_keys=True)
+        return
     spec = models.glm_nuts(N=N, P=P, family="bernoulli")
     r = measure(spec, "y", a.draws, loo_draws=a.loo_draws)
     r.update(N=N, P=P, bytes_per_draw=8 * N * P / r["batch"] + 8 * N, bytes_parent_pass=8 * N * P)
     res["glm"] = r
     print(json.dumps({"glm": r}), flush=True)
     del spec
-    G, D, rpg = 1248, 8, 4000 // div
     spec = models.hier_logit(G=G, D=D, rows_per_group=rpg)
     r = measure(spec, "y", a.draws, loo_draws=a.loo_draws)
     Nr = G * rpg
