@@ -401,6 +401,22 @@ int nuts_ppc_read(nuts_ppc *p, double *mean_i, double *var_i, double *n_lt_i, do
 int nuts_ppc_read_stats(nuts_ppc *p, double *T /* [n_draws][4] */, double *T_obs /* [4] */);
 void nuts_ppc_destroy(nuts_ppc *p);
 
+/* ---- convergence summary of a trace: `az.summary(idata, kind="all")` ---------------------------------------------------------------
+ * Per parameter, from its C chains of N draws: mean, sd (ddof = 1), the highest-density interval of probability hdi_prob (the
+ * narrowest interval of floor(hdi_prob C N) + 1 sorted draws, the first on ties), the Monte-Carlo standard errors of the mean and
+ * of the sd, rank-normalised split bulk-ESS, tail-ESS (the smaller of the ESS of the indicators of the pooled 5 % and 95 % quantiles)
+ * and rank-normalised split R-hat (the larger of bulk and folded) -- Vehtari, Gelman, Simpson, Carpenter, Buerkner 2021 as ArviZ
+ * implements them; pymc_amd/csrc/summary.h holds the definitions.  One workgroup per parameter sorts its draws in LDS, which sets
+ * nuts_summary_max_draws() = 8192 = the largest C N; beyond it, C < 1, N < 1 and hdi_prob outside (0, 1) are NUTS_E_ARG with a text in
+ * nuts_last_error().  A parameter with a non-finite draw has NaN in every column; with fewer than 4 draws per half chain the four ESS
+ * / MCSE columns are NaN, with a window floor(hdi_prob C N) of C N draws or more the two HDI columns.  Runs on the current device
+ * (nuts_set_device) and needs no model.  P is processed in blocks of the option NUTS_SUMMARY_BLOCK (1024) parameters, read at every
+ * call, which bound the device memory; a parameter's row depends on its own draws only, bit for bit. */
+#define NUTS_SUMMARY_COLS 9   /* mean sd hdi_lo hdi_hi mcse_mean mcse_sd ess_bulk ess_tail r_hat */
+int64_t nuts_summary_max_draws(void);
+int nuts_summary(const double *x /* host [C][N][P] */, int64_t C, int64_t N, int64_t P, double hdi_prob,
+                 double *out /* host [NUTS_SUMMARY_COLS][P] */);
+
 /* ---- chain: replaces BaseHMC/NUTS + potential + step adaptation ------------- */
 /* NUTS_POT_FULL covers QuadPotentialFull and QuadPotentialFullInv (quadpotential.py:633-725): the caller passes
  * the dense covariance C (velocity = C p) and the matrix W with potential.random() = W z

@@ -301,6 +301,8 @@ SYMBOLS = {
     "nuts_ppc_read": (C.c_int, [_VP, _PD, _PD, _PD, _PD, C.POINTER(C.c_int64)]),
     "nuts_ppc_read_stats": (C.c_int, [_VP, _PD, _PD]),
     "nuts_ppc_destroy": (None, [_VP]),
+    "nuts_summary_max_draws": (C.c_int64, []),
+    "nuts_summary": (C.c_int, [_PD, C.c_int64, C.c_int64, C.c_int64, C.c_double, _PD]),
 }
 
 _lib = None

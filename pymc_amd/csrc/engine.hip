@@ -26,6 +26,7 @@
 #include "mixture_kernel.h"
 #include "loglik_kernel.h"
 #include "predictive_kernel.h"
+#include "summary_kernel.h"
 #include "nuts_mi355.h"
 #include "pcg64_stream.h"
 #include "advi.h"
@@ -2767,6 +2768,50 @@ extern "C" void nuts_ppc_destroy(nuts_ppc* p) {
   hipStreamSynchronize(p->m->stream);
   p->m->n_waic--;
   ppc_free(p);
+}
+
+// ---- convergence summary of a trace (summary.h, summary_kernel.h) ---------------------------------------------------
+// No model: the draws are the caller's, on the host, [C][N][P] with the parameter fastest.  P is cut into blocks of NUTS_SUMMARY_BLOCK
+// parameters (read at every call), which bound the device memory at 2 * 8 C N bytes per parameter of a block; a parameter's row of
+// the result does not depend on the block it travelled in.
+static_assert(NUTS_SUMMARY_COLS == SM_COLS, "summary.h restates the column count of nuts_mi355.h");
+extern "C" int64_t nuts_summary_max_draws(void) { return SUM_MAX_S; }
+
+extern "C" int nuts_summary(const double* x, int64_t C, int64_t N, int64_t P, double hdi_prob, double* out) {
+  if (C < 1 || N < 1 || P < 0) { g_err = "nuts_summary: chains, draws >= 1 and parameters >= 0"; return NUTS_E_ARG; }
+  if (!(hdi_prob > 0.0 && hdi_prob < 1.0)) { g_err = "nuts_summary: hdi_prob must lie inside (0, 1)"; return NUTS_E_ARG; }
+  if (C > SUM_MAX_S || N > SUM_MAX_S || C * N > SUM_MAX_S) {
+    g_err = "nuts_summary: " + std::to_string(C) + " chains x " + std::to_string(N) + " draws exceed the " + std::to_string(SUM_MAX_S) +
+            " draws per parameter one workgroup sorts in LDS (nuts_summary_max_draws); a larger trace is out of scope";
+    return NUTS_E_ARG;
+  }
+  if (P == 0) return NUTS_OK;
+  if (!x || !out) { g_err = "null argument"; return NUTS_E_ARG; }
+  if (nuts_device_count() < 1) { g_err = "no HIP device visible: nuts_summary requires an MI355X (gfx950); there is no CPU fallback"; return NUTS_E_HIP; }
+  const int64_t blk = env_int("NUTS_SUMMARY_BLOCK", 1024);
+  if (blk < 1) { g_err = "NUTS_SUMMARY_BLOCK must be at least 1"; return NUTS_E_ARG; }
+  const int64_t S = C * N, B = std::min(P, blk);
+  double* raw = dev_alloc<double>((size_t)(S * B));   // [S][b], as uploaded
+  double* xt = dev_alloc<double>((size_t)(S * B));    // [b][S]
+  double* res = dev_alloc<double>((size_t)(SM_COLS * B));
+  hipError_t e = raw && xt && res ? hipSuccess : hipErrorOutOfMemory;
+  for (int64_t p0 = 0; p0 < P && e == hipSuccess; p0 += B) {
+    const int64_t b = std::min(B, P - p0);
+    e = hipMemcpy2D(raw, (size_t)b * sizeof(double), x + p0, (size_t)P * sizeof(double), (size_t)b * sizeof(double), (size_t)S, hipMemcpyHostToDevice);
+    if (e != hipSuccess) break;
+    hipLaunchKernelGGL(k_summary_transpose, dim3((unsigned)((b + SUM_TILE - 1) / SUM_TILE), (unsigned)((S + SUM_TILE - 1) / SUM_TILE)), dim3(SUM_BLOCK), 0, 0,
+                       (const double*)raw, S, b, xt);
+    hipLaunchKernelGGL(k_summary, dim3((unsigned)b), dim3(SUM_BLOCK), 0, 0, (const double*)xt, (int)C, (int)N, hdi_prob, res, b);
+    e = hipGetLastError();   // (a launch the runtime refuses -- k_summary's LDS -- is reported here, not as a fault)
+    if (e == hipSuccess) e = hipStreamSynchronize(0);
+    if (e == hipSuccess)
+      e = hipMemcpy2D(out + p0, (size_t)P * sizeof(double), res, (size_t)b * sizeof(double), (size_t)b * sizeof(double), SM_COLS, hipMemcpyDeviceToHost);
+  }
+  if (raw) hipFree(raw);
+  if (xt) hipFree(xt);
+  if (res) hipFree(res);
+  HIPCHK_RET(e, "nuts_summary", NUTS_E_HIP);
+  return NUTS_OK;
 }
 
 static void profile_enable(nuts_model* m, bool on, int sample_every, size_t max_pairs) {

@@ -547,6 +547,7 @@ def sample(
     lockstep: Optional[bool] = None,
     log_likelihood: bool = False,
     posterior_predictive: bool = False,
+    summary: bool = False,
     **step_kwargs,
 ):
     """Reduced `pm.sample` (mcmc.py:620-1190) returning raw arrays (and, with ``return_multitrace=True``, the reference's
@@ -588,6 +589,11 @@ def sample(
     (pymc_amd/predictive.py) under the key `np.random.SeedSequence(random_seed).generate_state(1, np.uint64)[0]`; draw d of the model's
     chain number c (``result["chains"]``: also where a rank holds only its own chains) is draw c * draws + d of the generator's stream.
     ``random_seed=None`` takes a fresh key, in every process its own.  A model with an observed variable it cannot draw from is refused before sampling.
+
+    ``summary`` (`az.summary` of the finished trace): ``result["summary"]`` = {"names": [...], "mean": ..., "sd": ..., "hdi_lo": ...,
+    "hdi_hi": ..., "mcse_mean": ..., "mcse_sd": ..., "ess_bulk": ..., "ess_tail": ..., "r_hat": ...} with one row per element of every
+    variable, computed on the device (pymc_amd/summary.py) from the draws the result holds after the gather; a rank left with no
+    draws gets none.
     """
     rank, world, local = _dist_info()
     from pymc_amd.lowering import as_model_spec
@@ -864,6 +870,10 @@ def sample(
         f = getattr(step, "_logp_dlogp_func", None)
         result["posterior_predictive"] = sample_posterior_predictive(spec, result["draws"], random_seed=seed_from(random_seed), device=device, chain_ids=result["chains"],
                                                                      func=f if hasattr(f, "posterior_predictive") else None)
+    if summary and result["draws"] is not None and np.shape(result["draws"])[0] > 0:
+        from pymc_amd.summary import summary as summarize_trace
+
+        result["summary"] = summarize_trace(spec, result["draws"], device=device)
     return result
 
 
