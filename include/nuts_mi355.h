@@ -320,6 +320,9 @@ int64_t nuts_model_algorithmic_bytes(const nuts_model *m);
  *                         "edge_pair_turns" the most changes of direction between the doublings of one tree of depth >= 4 so far,
  *                         "edge_pair_dropped" the leaves evaluated ahead for a doubling their tree never reached,
  *                         "edge_pair_ring_full" the leaves that streamed alone only because the ring had no room,
+ *                         "edge_pair_packed" 1 when the paired launch streams the packed tiles (0: the raw ones),
+ *                         "edge_pair_rounds" ceil(workgroups of the paired launch / workgroups of its kernel the device holds at
+ *                         once, as the runtime reports it): 1 when the whole launch is resident,
  *   "rows_waves", "lean", "single_workgroup_ok",
  *   "loglik_batch"        draws per batch of nuts_model_loglik / nuts_waic_update; "loglik_stage_bytes" the bytes of the one
  *                         [batch][N] block of pointwise values the model holds (0 before the first such call). */

@@ -95,6 +95,8 @@ static T* dev_upload(const T* src, size_t count) {
 //   * an end never holds more leaves than its next doubling has (`cap`: that doubling must be one the look-ahead knows the
 //     direction of), nor more than the ring; shadow leaf k is always leaf k of that doubling, so it is consumed in order.
 enum { EP_PLAIN = 0, EP_PAIRED = 1, EP_REPLAY = 2 };
+// the paired launch's kernel: the packed tiles where the model has them, else the raw ones with seven or eight stored columns
+enum { EPV_PACKED = 0, EPV_RAW7 = 1, EPV_RAW8 = 2 };
 struct EdgePlan {
   int ring = 64;
   int side = 0, n = 0;      // outstanding shadow leaves: their end (+1 right, -1 left) and how many
@@ -190,6 +192,8 @@ struct nuts_model {
   // edge pairing: the shadow sequence's records, block partials, local parts (its tickets: the second half of
   // lg.ga_ticket) and the ring of parked wave sums; allocated when the model is eligible
   int ep_ok = 0, ep_par = 0;
+  int ep_variant = 0;         // EPV_*: which instantiation of k_rows_ga_multi the paired launch is (chosen when the model is built)
+  int ep_rounds = 0;          // rounds the paired grid needs at that kernel's residency: ceil((GAM_MAXC + G) / resident workgroups)
   double *ep_ring = nullptr, *ep_part = nullptr, *ep_bpart = nullptr, *ep_def_loc = nullptr;
   int64_t ep_ring_bytes = 0, ep_shadows = 0, ep_replays = 0;
   int64_t ep_dropped = 0;     // shadow leaves no tree used: outstanding when their tree ended, or replayed only by a look-ahead doubling behind its end
@@ -648,7 +652,8 @@ static void launch_dense(nuts_model* m, const ArenaDev& A, const EvalIO& io, int
     const nuts_model::EpLaunch ep = m->ep_launch;
     m->ep_launch.kind = EP_PLAIN;
     if (ep.kind == EP_PAIRED) {
-      // edge pairing: this leaf and the next leapfrog of the trajectory's other end in ONE pass over the (raw) tiles
+      // edge pairing: this leaf and the next leapfrog of the trajectory's other end in ONE pass over the tiles the chain's own
+      // launch streams (packed where the model has the packed copy), every workgroup resident at once
       GaMultiArgs<2, true> ma;
       GaLeafArgs& L = ma.c[0];
       L.A = A; L.io = io; L.cio = ga.cio; L.Emax = Emax; L.st = st;
@@ -663,8 +668,11 @@ static void launch_dense(nuts_model* m, const ArenaDev& A, const EvalIO& io, int
       ma.rev = rev; ma.pad = 0;
       ma.ring = m->ep_ring + (size_t)ep.slot * md.lg.G * GA_RING_DOUBLES(8);
       const dim3 pgrid(GAM_MAXC + md.lg.G);
-      if (md.lg.ga_dx == 7) hipLaunchKernelGGL((k_rows_ga_multi<2, 3, 7, true>), pgrid, block, 0, m->stream, md, ma);
-      else hipLaunchKernelGGL((k_rows_ga_multi<2, 3, 8, true>), pgrid, block, 0, m->stream, md, ma);
+      switch (m->ep_variant) {
+        case EPV_PACKED: hipLaunchKernelGGL((k_rows_ga_multi<2, 4, 7, true, 1>), pgrid, block, 0, m->stream, md, ma); break;
+        case EPV_RAW7: hipLaunchKernelGGL((k_rows_ga_multi<2, 4, 7, true>), pgrid, block, 0, m->stream, md, ma); break;
+        default: hipLaunchKernelGGL((k_rows_ga_multi<2, 4, 8, true>), pgrid, block, 0, m->stream, md, ma); break;
+      }
       m->ep_shadows++;
     } else if (ep.kind == EP_REPLAY) {
       // ... and a leaf evaluated that way: the launch without its stream
@@ -1459,7 +1467,7 @@ static bool build_lins(nuts_model* m, const nuts_model_spec* s, const CompiledSp
 
 // Logit rows, group-aligned / group-block layout (rows_ga_kernel.h, rows_gb_kernel.h): X in tiles per (group, wave) chunk.
 static bool build_rows_group(nuts_model* m, const nuts_model_spec* s, const std::vector<int64_t>& gptr, const std::vector<int32_t>& tile0,
-                             int64_t maxT, int W, int gpw) {
+                             int64_t maxT, int W, int gpw, int cus) {
   RowsDev& lg = m->md.lg;
   const int n = m->md.n, D = lg.D, SPAN = WAVE * m->rows_rpl;
   const int64_t n_tiles = tile0[lg.G];
@@ -1605,6 +1613,18 @@ static bool build_rows_group(nuts_model* m, const nuts_model_spec* s, const std:
       hipMemset(m->ep_bpart, 0, bpart_len * sizeof(double));
       hipMemset(m->ep_def_loc, 0, 2 * 4 * (size_t)MAX_DEFERRED * sizeof(double));
       m->ep_ok = 1; m->ep_ring_bytes = (int64_t)(ring_len * sizeof(double));
+      // the paired launch's kernel, and how many rounds its grid needs at the residency the runtime reports for it
+      m->ep_variant = lg.ga_pack ? EPV_PACKED : (DX == 7 ? EPV_RAW7 : EPV_RAW8);
+      const void* kfn = nullptr;
+      switch (m->ep_variant) {
+        case EPV_PACKED: kfn = (const void*)k_rows_ga_multi<2, 4, 7, true, 1>; break;
+        case EPV_RAW7: kfn = (const void*)k_rows_ga_multi<2, 4, 7, true>; break;
+        default: kfn = (const void*)k_rows_ga_multi<2, 4, 8, true>; break;
+      }
+      int per_cu = 0;
+      if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kfn, WAVE * W, 0) != hipSuccess || per_cu < 1) { (void)hipGetLastError(); per_cu = 0; }
+      const int64_t slots = (int64_t)per_cu * cus, wgs = (int64_t)GAM_MAXC + lg.G;
+      m->ep_rounds = slots > 0 ? (int)((wgs + slots - 1) / slots) : 0;
     } else (void)hipGetLastError();   // (a device that cannot hold the ring runs today's schedule)
   }
   m->rows_grid = gpw ? lg.ga_nblk : lg.G;
@@ -1779,7 +1799,7 @@ static bool build_rows(nuts_model* m, const nuts_model_spec* s, int cus) {
   }
   if (gpw) { use = true; W = 1; }   // (layout: one chunk per group)
   const bool group = use && n_tiles * (int64_t)SPAN < ((int64_t)1 << 31) && (gpw || lg.G <= 32 * 8 * GA_MAXCHUNK);
-  if (!(group ? build_rows_group(m, s, gptr, tile0, maxT, W, gpw) : build_rows_spans(m, s, cus))) return false;
+  if (!(group ? build_rows_group(m, s, gptr, tile0, maxT, W, gpw, cus) : build_rows_spans(m, s, cus))) return false;
   m->alg_bytes += lg.N * (8 * (int64_t)D + 1 + 4);  // X row + y + group id per row
   return true;
 }
@@ -2023,8 +2043,8 @@ static bool model_build(nuts_model* m, const nuts_model_spec* s) {
   if (m->orphan_elems > 4 * VEC_THREADS * (int64_t)md.nblk)
     md.nblk = (int)std::min<int64_t>(256, (m->orphan_elems + 4 * VEC_THREADS - 1) / (4 * VEC_THREADS));
   md.tick_j = env_int("NUTS_TICK_J", -1);
-  md.ticks = m->keep(dev_alloc<long long>(64));
-  hipMemset(md.ticks, 0, 64 * sizeof(long long));
+  md.ticks = m->keep(dev_alloc<long long>(TICK_SLOTS));
+  hipMemset(md.ticks, 0, TICK_SLOTS * sizeof(long long));
   md.part_stride = PART_STRIDE;
   m->vector_one_xcd = env_int("NUTS_VECTOR_ONE_XCD", 0);
   md.part = m->keep(dev_alloc<double>((size_t)md.nblk * PART_STRIDE));
@@ -2132,6 +2152,30 @@ extern "C" int nuts_model_debug_ticks(nuts_model* m, int64_t* out) {
   if (!m || !out) return NUTS_E_ARG;
   HIPCHK(hipStreamSynchronize(m->stream));
   HIPCHK(hipMemcpy(out, m->md.ticks, 64 * sizeof(long long), hipMemcpyDeviceToHost));
+#ifdef NUTS_KTIMING
+  // slots 40 .. 47, the last edge-pairing launch (rows_ga_multi_kernel.h stamps every group workgroup): workgroups stamped, the
+  // earliest start, the earliest and the latest retirement, how many workgroups started after the earliest retirement, the latest
+  // such start and the sum of their delays behind it, the latest start of all (tools/edge_pair_ticks.py)
+  if (m->md.has_logit && m->md.lg.ga && m->ep_ok) {
+    const int nw = std::min(m->md.lg.G, EP_TICK_WG);
+    std::vector<long long> wg(2 * (size_t)nw);
+    HIPCHK(hipMemcpy(wg.data(), m->md.ticks + 64, wg.size() * sizeof(long long), hipMemcpyDeviceToHost));
+    long long n = 0, s0 = 0, e0 = 0, e1 = 0, s1 = 0;
+    for (int g = 0; g < nw; ++g) {
+      const long long a = wg[2 * (size_t)g], b = wg[2 * (size_t)g + 1];
+      if (a == 0 || b < a) continue;
+      s0 = n ? std::min(s0, a) : a; e0 = n ? std::min(e0, b) : b; e1 = n ? std::max(e1, b) : b; s1 = n ? std::max(s1, a) : a;
+      ++n;
+    }
+    long long late = 0, late_max = 0, late_sum = 0;
+    for (int g = 0; g < nw; ++g) {
+      const long long a = wg[2 * (size_t)g], b = wg[2 * (size_t)g + 1];
+      if (a == 0 || b < a || a <= e0) continue;
+      ++late; late_max = std::max(late_max, a); late_sum += a - e0;
+    }
+    out[40] = n; out[41] = s0; out[42] = e0; out[43] = e1; out[44] = late; out[45] = late_max; out[46] = late_sum; out[47] = s1;
+  }
+#endif
   return NUTS_OK;
 }
 
@@ -2152,6 +2196,9 @@ extern "C" int nuts_model_get_scalar(const nuts_model* m, const char* name, doub
   else if (k == "edge_pair_turns") *out = m->ep_turns;
   else if (k == "edge_pair_dropped") *out = (double)m->ep_dropped;
   else if (k == "edge_pair_ring_full") *out = (double)m->ep_ring_full;
+  // the paired launch streams the packed tiles; rounds its grid needs at the kernel's residency (1: every workgroup resident at once)
+  else if (k == "edge_pair_packed") *out = m->ep_ok && m->ep_variant == EPV_PACKED ? 1.0 : 0.0;
+  else if (k == "edge_pair_rounds") *out = m->ep_ok ? m->ep_rounds : 0;
   else if (k == "rows_aux_workgroups") *out = m->md.lg.ga ? m->md.lg.ga_naux : 0;
   else if (k == "mixture_workgroups") *out = m->md.has_mix ? m->md.mix.nwg : 0;
   else if (k == "glm_workgroups") *out = m->md.has_glm ? m->md.glm.nwg : 0;

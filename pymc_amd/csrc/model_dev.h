@@ -329,7 +329,18 @@ __device__ __forceinline__ long long tick_now() {   // drains outstanding memory
   return (long long)t;
 }
 #define TICK(md, cond, slot) do { if (cond) (md).ticks[slot] = tick_now(); } while (0)
+// (`s_memtime` counts shader cycles of the workgroup's own XCD: stamps of DIFFERENT workgroups are compared on the constant
+// 100 MHz clock instead, which all XCDs share)
+__device__ __forceinline__ long long tick_real() {
+  unsigned long long t;
+  asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t) :: "memory");
+  return (long long)t;
+}
+// behind the 64 phase slots: {start, retirement} of every group workgroup of the last edge-pairing launch (rows_ga_multi_kernel.h)
+#define EP_TICK_WG 4096
+#define TICK_SLOTS (64 + 2 * EP_TICK_WG)
 #else
+#define TICK_SLOTS 64
 #define TICK(md, cond, slot) do { } while (0)
 #endif
 

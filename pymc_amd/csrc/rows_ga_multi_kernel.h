@@ -76,14 +76,32 @@ __device__ __forceinline__ void gam_load(const double* base /* first element of 
   t.y = *reinterpret_cast<const uint16_t*>(ybase + 2 * lane);
 }
 
+// The seven planes of a packed tile (rows_pack.h; GA_PACKED_LOADS of rows_ga_kernel.h spells the same offsets) with ORDINARY loads,
+// for the reason above: six planes of four dwords per lane, 1 KiB apart, then the plane of one dword per lane.
+__device__ __forceinline__ void gam_load_packed(const uint32_t* base /* first dword of the tile */, int lane, GaTileRegsP& t) {
+  const ga_v4u* p = reinterpret_cast<const ga_v4u*>(base) + lane;
+#pragma unroll
+  for (int k = 0; k < 6; ++k) t.p[k] = p[k * WAVE];
+  t.last = base[6 * 4 * WAVE + lane];
+}
+
 // D = 8 covariates, two rows per lane, two tile buffers per wave; DX stored columns (7: the intercept column is not stored).  Grid: GAM_MAXC control workgroups + G group workgroups; block: the W waves of the
 // model's layout (a wave's chunk of tiles is fixed when the model is created).
-template <int NC, int OCC, int DX, bool SH = false>
+// Edge pairing (SH) runs at FOUR waves per SIMD: GAM_MAXC + G workgroups of W waves are then resident at once, as the plain
+// launch's are (rows_ga_kernel.h: "G workgroups of W waves must all be resident"; at three waves per SIMD 1024 of the benchmark's
+// 1256 workgroups were, and the rest ran as a second round on a nearly empty chip).  128 registers hold ONE tile buffer and the
+// rows of a lane one after the other: a tile is decoded into `xx`, the wave's next tile is requested into the same registers, and
+// both coefficient vectors are evaluated on `xx` while it arrives.  PK (SH only): the tiles are the packed ones the chain's own
+// launch streams (R.Xp, 6400 B per tile instead of 7296), decoded and patched exactly as k_rows_ga does.
+template <int NC, int OCC, int DX, bool SH = false, int PK = 0>
 __global__ __launch_bounds__(64 * GA_MAXW, OCC) void k_rows_ga_multi(ModelDev md, GaMultiArgs<NC, SH> ma) {
   constexpr int D = 8, RPL = 2, SPAN = WAVE * RPL, PIPE = 2;
   static_assert(!SH || NC == 2, "edge pairing: the chain's leaf and one shadow leaf");
+  static_assert(!SH || OCC == 4, "edge pairing: four waves per SIMD, the whole grid resident");
+  static_assert(!PK || (SH && DX == 7), "packed tiles: the edge-pairing launch of a model with seven stored columns");
+  constexpr bool ONE = SH;   // one tile buffer, re-requested ahead of the arithmetic; rows one after the other
   typedef GaMultiArgs<NC, SH> Args;
-  typedef typename GaTileSel<DX>::type Tile;
+  typedef typename GaTileSel<DX, PK>::type Tile;
   const RowsDev& R = md.lg;
   if ((int)blockIdx.x < GAM_MAXC) {   // control workgroups
     int ci = -1;
@@ -95,6 +113,9 @@ __global__ __launch_bounds__(64 * GA_MAXW, OCC) void k_rows_ga_multi(ModelDev md
     return;
   }
   const int g = (int)blockIdx.x - GAM_MAXC;
+#ifdef NUTS_KTIMING
+  const long long tk_top = tick_real();   // (lab build, tools/edge_pair_ticks.py: when this workgroup started)
+#endif
   const int rev = ma.rev;
   const int tid = threadIdx.x, lane = tid & (WAVE - 1), w = __builtin_amdgcn_readfirstlane(tid >> 6), W = (int)blockDim.x >> 6;
   __shared__ double s_acc[NC][GA_MAXW][2][D + 1];   // [chain][wave][first / second half of its tiles][d/dbeta, log-lik]
@@ -107,18 +128,20 @@ __global__ __launch_bounds__(64 * GA_MAXW, OCC) void k_rows_ga_multi(ModelDev md
 
   // ---- geometry of this wave's stream (as k_rows_ga) ----
   int T; int64_t ng, cbase;
-  if (R.ga_T_uni > 0) { T = R.ga_T_uni; ng = R.ga_ng_uni; cbase = (int64_t)(g * W + w) * R.ga_cstride_uni; }
+  int tg0;   // packed tiles: index of the group's first tile in the per-tile exception table
+  if (R.ga_T_uni > 0) { T = R.ga_T_uni; ng = R.ga_ng_uni; cbase = (int64_t)(g * W + w) * (PK ? R.ga_pstride_uni : R.ga_cstride_uni); tg0 = g * T; }
   else {
-    T = __builtin_amdgcn_readfirstlane(R.ga_tile0[g + 1] - R.ga_tile0[g]);
+    tg0 = __builtin_amdgcn_readfirstlane(R.ga_tile0[g]);
+    T = __builtin_amdgcn_readfirstlane(R.ga_tile0[g + 1]) - tg0;
     ng = __builtin_amdgcn_readfirstlane((int)(R.gptr[g + 1] - R.gptr[g]));
-    const int64_t cb = R.ga_coff[g * W + w];
+    const int64_t cb = (PK ? R.ga_pcoff : R.ga_coff)[g * W + w];
     cbase = ((int64_t)__builtin_amdgcn_readfirstlane((int)(cb >> 32)) << 32) | (uint32_t)__builtin_amdgcn_readfirstlane((int)(cb & 0xffffffffll));
   }
   const int c0 = (int)((int64_t)w * T / W), c2 = (int)((int64_t)(w + 1) * T / W);
   const int n = c2 - c0;
   const int nA = (n + 1) / 2;
   const int nsw = rev ? n - nA : nA;
-  constexpr int64_t TS = (int64_t)DX * SPAN;
+  constexpr int64_t TS = PK ? RP_TILE_DWORDS : (int64_t)DX * SPAN;   // doubles per tile (packed: dwords)
   auto local_at = [&](int i) { return rev ? (i < nsw ? nA + i : i - nsw) : i; };
   auto tile_at = [&](int i) { return cbase + (int64_t)local_at(i) * TS; };
   const int l_last = (c2 == T) ? n - 1 : -1;
@@ -168,9 +191,15 @@ __global__ __launch_bounds__(64 * GA_MAXW, OCC) void k_rows_ga_multi(ModelDev md
   // buffer is what pushed the allocator into spilling inside the loop (107 us per launch against 80 for three chains, rocprofv3
   // r05c): one buffer then, the wave's next tile is requested when the current one has been evaluated -- at ~1.3 us of arithmetic
   // per tile and twelve waves per CU the other waves cover the wait.
-  constexpr bool TWO = NC <= 3;
+  constexpr bool TWO = NC <= 3 && !ONE;
   Tile ta, tb;
-  {
+  uint64_t ea = 0;   // packed tiles: the exception range of the tile in flight (a scalar load issued with the tile)
+  const int te0 = tg0 + c0;
+  // (a wave without tiles requests the chunk's first tile slot anyway: the layout keeps one tile of slack behind every chunk)
+  if constexpr (PK) {
+    gam_load_packed(R.Xp + tile_at(0), lane, ta);
+    ea = ga_exc_range(R.ga_pexc_idx, te0 + local_at(0));
+  } else {
     const int64_t o0 = tile_at(0), o1 = tile_at(min(1, max(n - 1, 0)));
     gam_load<DX>(R.Xt + o0, R.y + o0 / DX, lane, ta);
     if constexpr (TWO) gam_load<DX>(R.Xt + o1, R.y + o1 / DX, lane, tb);
@@ -216,8 +245,14 @@ __global__ __launch_bounds__(64 * GA_MAXW, OCC) void k_rows_ga_multi(ModelDev md
     };
     const int nm1 = n - 1;
     auto issue = [&](int i, Tile& t) {   // (unconditional: past the end it re-reads the wave's last tile)
-      const int64_t off = tile_at(min(i, nm1));
-      gam_load<DX>(R.Xt + off, R.y + off / DX, lane, t);
+      const int ii = min(i, nm1);
+      if constexpr (PK) {
+        gam_load_packed(R.Xp + tile_at(ii), lane, t);
+        ea = ga_exc_range(R.ga_pexc_idx, te0 + local_at(ii));
+      } else {
+        const int64_t off = tile_at(ii);
+        gam_load<DX>(R.Xt + off, R.y + off / DX, lane, t);
+      }
     };
 #define GAM_STAGE(TT, I)                                                                     \
     {                                                                                        \
@@ -229,7 +264,26 @@ __global__ __launch_bounds__(64 * GA_MAXW, OCC) void k_rows_ga_multi(ModelDev md
       /* (two chains and more: the rows of a lane side by side, logit_row2 -- the launch is bound by dependent fp64 issue, not HBM) */ \
       _Pragma("unroll") for (int c = 0; c < NC; ++c) ga_tile<8, 2, (NC == 2)>(xx, yy, beta[c], nv, lane, acc[c], lp[c]); \
     }
-    if constexpr (TWO) {
+    if constexpr (ONE) {
+      // one buffer, four waves per SIMD: decode (packed: and patch) the tile into `xx`, re-request the buffer, then the arithmetic
+      uint32_t ebase20 = 0;
+      if constexpr (PK) ebase20 = R.ga_pack_ebase20;
+      for (int i = 0; i < n; ++i) {
+        if (i == nsw) flush();
+        double xx[8][2];
+        if constexpr (PK) {
+          ga_unpack(ta, ebase20, xx);
+          if ((uint32_t)(ea >> 32) != 0) ga_patch(R.ga_pexc, ea, lane, xx);
+        } else {
+          ga_unpack(ta, xx);
+        }
+        const uint32_t yy = ga_ybits(ta);
+        const int nv = local_at(i) == l_last ? n_last : SPAN;
+        issue(i + 1, ta);
+#pragma unroll
+        for (int c = 0; c < NC; ++c) ga_tile<8, 2>(xx, yy, beta[c], nv, lane, acc[c], lp[c]);
+      }
+    } else if constexpr (TWO) {
       for (int i = 0; i < n; i += 2) {
         GAM_STAGE(ta, i)
         if (i + 1 >= n) break;
@@ -287,4 +341,10 @@ __global__ __launch_bounds__(64 * GA_MAXW, OCC) void k_rows_ga_multi(ModelDev md
     ga_block_partial<D>(R, Tm.c[c].ga_part, Tm.c[c].ga_bpart, Tm.c[c].par, g, true, s_info[c], s_cp);
     __syncthreads();
   }
+#ifdef NUTS_KTIMING
+  if constexpr (SH) {   // start and retirement of every group workgroup of the last paired launch (nuts_model_debug_ticks sums them up)
+    __syncthreads();
+    if (tid == 0 && g < EP_TICK_WG) { md.ticks[64 + 2 * g] = tk_top; md.ticks[64 + 2 * g + 1] = tick_real(); }
+  }
+#endif
 }
