@@ -48,8 +48,11 @@ __device__ __forceinline__ void rows_flush(double (&acc)[D], double* __restrict_
 //   exp(x), x <= 0     k = rint(x log2 e), r = x - k ln 2 (two-part), Taylor to r^13 (|r| <= 0.347: 4e-18), v_ldexp_f64
 //   1 / t, t in (1,3]  v_rcp_f64 seed + two Newton steps (no scaling needed in this range)
 //   log1p(e)           = 2 atanh(s), s = e / (2 + e) <= 1/3: 2 s + 2 s z P(z), z = s^2, P of degree 9 (fit on [0, 1/9], 7e-18)
-// 73 fp64 operations per row instead of ~190 + 150 moves; every one of them within about an ulp of the library's result
-// (scratch emulation without fma: 1 / 3 / 4 ulp), far inside the 1e-9 the log-density is held to against the oracle.
+// 73 fp64 operations per row instead of ~190 + 150 moves.  Accuracy, measured on the device against mpmath at 809 values of eta
+// out to the clamp and beyond (tests/test_gpu_logit_edges.py, profiles/logit_edges.json): lp within 1.8 and r within
+// 1.4 of (one ulp of the result + what one ulp of eta moves it) in every regime, the denormal results of the ldexp included.  The
+// exception is in the forms below, not in the three functions: for y = 1 and eta > 0, lp = eta - (eta + log1p(e)) and
+// r = 1 - 1 / (1 + e) cancel, and carry an absolute error of half an ulp of eta / of 1 where the truth is of size exp(-eta).
 // -DNUTS_LOGIT_LIBM restores the library forms (A/B measurements).
 __device__ __forceinline__ double rcp_nr(double x) {   // 1 / x for x in [1, 4]
   double y = __builtin_amdgcn_rcp(x);
