@@ -403,6 +403,31 @@ int nuts_ppc_update(nuts_ppc *p, const double *q, int64_t S);
 int nuts_ppc_read(nuts_ppc *p, double *mean_i, double *var_i, double *n_lt_i, double *n_eq_i, int64_t *n_draws);
 int nuts_ppc_read_stats(nuts_ppc *p, double *T /* [n_draws][4] */, double *T_obs /* [4] */);
 void nuts_ppc_destroy(nuts_ppc *p);
+/* LOO predictive checks (`az.loo_pit`, the LOO predictive mean and variance of each observation): a SECOND pass over the draws of
+ * a finished nuts_psis.  Once all n_draws are in, the PSIS state fixes the normalised Pareto-smoothed weight w[s][i] of every draw:
+ * a draw outside the tail keeps its raw weight, a draw of the tail takes the generalised-Pareto quantile of its rank in the sorted
+ * column (pymc_amd/csrc/psis.h, psis_fit / psis_weight).  Tied values share the arithmetic mean of the weights of the ranks they
+ * occupy, so the result does not depend on the order of the draws (ArviZ's does; the two agree when no value repeats).  Per batch
+ * the pass evaluates the log-likelihood, looks the weights up, evaluates the replicates of nuts_model_predictive and folds, per
+ * observation, sum w, sum w^2, sum w [y_rep < y], sum w [y_rep == y] and the weighted mean and M2 of y_rep.  The state is
+ * 8 (7 + 6 + B) N bytes, B = 8 the batch (plus 8 N for y_obs of a factor or of the logit rows); no [S][N] matrix exists anywhere.
+ *   nuts_loo_pit_create: NULL (text in nuts_last_error()) unless `p` holds all of its n_draws, and where nuts_ppc_create refuses
+ *                        the node.  The handle BORROWS p's sorted column and fit: `p` must outlive it.
+ *   nuts_loo_pit_update: the draws of the first pass again, in any split (the state is bitwise that after one call); the replicate
+ *                        of a draw is addressed by its GLOBAL number draw0 + position in the call, so it is the value
+ *                        nuts_model_predictive returns under the same seed and numbering.  NUTS_E_ARG past n_draws in total.
+ *                        Draws the first pass did not see are not detected here: sum_w then differs from 1.
+ *   nuts_loo_pit_read:   p_lt = sum w [y_rep < y], p_eq = sum w [y_rep == y] (LOO-PIT = p_lt + p_eq), the weighted mean and
+ *                        population variance of y_rep, sum_w (1 after a complete pass) and sum_w2 (1 / sum_w2: the effective sample
+ *                        size of the weights); any of them may be NULL.  An observation whose fit is degenerate (ll = -inf at some
+ *                        draw) or poisoned (a NaN or +inf value) has NaN in every column.  A NaN replicate makes mean and var of
+ *                        its observation NaN; the weighted counts never see it.
+ * Destroy the handle before its nuts_psis. */
+typedef struct nuts_loo_pit nuts_loo_pit;
+nuts_loo_pit *nuts_loo_pit_create(nuts_psis *p, uint64_t seed);
+int nuts_loo_pit_update(nuts_loo_pit *h, const double *q, int64_t S, int64_t draw0);
+int nuts_loo_pit_read(nuts_loo_pit *h, double *p_lt, double *p_eq, double *mean, double *var, double *sum_w, double *sum_w2, int64_t *n_draws);
+void nuts_loo_pit_destroy(nuts_loo_pit *h);
 
 /* ---- convergence summary of a trace: `az.summary(idata, kind="all")` ---------------------------------------------------------------
  * Per parameter, from its C chains of N draws: mean, sd (ddof = 1), the highest-density interval of probability hdi_prob (the

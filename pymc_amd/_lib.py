@@ -301,6 +301,10 @@ SYMBOLS = {
     "nuts_ppc_read": (C.c_int, [_VP, _PD, _PD, _PD, _PD, C.POINTER(C.c_int64)]),
     "nuts_ppc_read_stats": (C.c_int, [_VP, _PD, _PD]),
     "nuts_ppc_destroy": (None, [_VP]),
+    "nuts_loo_pit_create": (_VP, [_VP, C.c_uint64]),
+    "nuts_loo_pit_update": (C.c_int, [_VP, _PD, C.c_int64, C.c_int64]),
+    "nuts_loo_pit_read": (C.c_int, [_VP, _PD, _PD, _PD, _PD, _PD, _PD, C.POINTER(C.c_int64)]),
+    "nuts_loo_pit_destroy": (None, [_VP]),
     "nuts_summary_max_draws": (C.c_int64, []),
     "nuts_summary": (C.c_int, [_PD, C.c_int64, C.c_int64, C.c_int64, C.c_double, _PD]),
 }

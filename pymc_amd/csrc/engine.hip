@@ -26,6 +26,7 @@
 #include "mixture_kernel.h"
 #include "loglik_kernel.h"
 #include "predictive_kernel.h"
+#include "loo_pit_kernel.h"
 #include "summary_kernel.h"
 #include "nuts_mi355.h"
 #include "pcg64_stream.h"
@@ -2493,6 +2494,7 @@ struct nuts_psis {
   double reff;
   int K1;
   double *keep, *acc;   // [K1][N] ascending per column, +inf where empty; [4][N]: m, r of ll, m_rest, r_rest of -ll
+  double* fit;          // [PSIS_FIT_FIELDS][N], the fit as a record (k_psis_fit): nullptr until psis_ensure_fit is asked for it
 };
 
 extern "C" nuts_psis* nuts_psis_create(nuts_model* m, int32_t kind, int32_t index, int64_t n_draws, double reff) {
@@ -2505,7 +2507,7 @@ extern "C" nuts_psis* nuts_psis_create(nuts_model* m, int32_t kind, int32_t inde
             " values per observation, more than the cap of " + std::to_string(PSIS_K1_MAX);
     return nullptr;
   }
-  auto* p = new nuts_psis{m, kind, index, N, 0, n_draws, reff, (int)K1, nullptr, nullptr};
+  auto* p = new nuts_psis{m, kind, index, N, 0, n_draws, reff, (int)K1, nullptr, nullptr, nullptr};
   const size_t n1 = (size_t)std::max<int64_t>(N, 1);
   if (hipMalloc((void**)&p->keep, (size_t)K1 * n1 * sizeof(double)) != hipSuccess || hipMalloc((void**)&p->acc, 4 * n1 * sizeof(double)) != hipSuccess) {
     (void)hipGetLastError();
@@ -2580,8 +2582,27 @@ extern "C" void nuts_psis_destroy(nuts_psis* p) {
   hipStreamSynchronize(p->m->stream);
   if (p->keep) hipFree(p->keep);
   if (p->acc) hipFree(p->acc);
+  if (p->fit) hipFree(p->fit);
   p->m->n_waic--;
   delete p;
+}
+
+// The fit of every observation as a record, once, on request (nuts_loo_pit_create); stream-ordered.  All n_draws must be in.
+static int psis_ensure_fit(nuts_psis* p) {
+  if (p->fit) return NUTS_OK;
+  if (p->count != p->n_draws) {
+    g_err = "PSIS fit: " + std::to_string(p->count) + " of " + std::to_string(p->n_draws) + " draws are in (the tail is sized for all of them)";
+    return NUTS_E_ARG;
+  }
+  const int64_t N = p->N;
+  if (hipMalloc((void**)&p->fit, PSIS_FIT_FIELDS * (size_t)std::max<int64_t>(N, 1) * sizeof(double)) != hipSuccess) {
+    (void)hipGetLastError(); p->fit = nullptr; g_err = "PSIS fit: device allocation failed"; return NUTS_E_HIP;
+  }
+  if (N > 0)
+    hipLaunchKernelGGL(k_psis_fit, dim3((unsigned)((N + PSIS_FIN_BLOCK - 1) / PSIS_FIN_BLOCK)), dim3(PSIS_FIN_BLOCK), 0, p->m->stream,
+                       (const double*)p->keep, (const double*)p->acc, N, p->K1, p->n_draws, p->fit);
+  HIPCHK(hipGetLastError());
+  return NUTS_OK;
 }
 
 // ---- posterior predictive and its streaming checks (predictive.h, predictive_kernel.h) ----------------------------------------------
@@ -2699,6 +2720,25 @@ extern "C" int nuts_model_predictive(nuts_model* m, int32_t kind, int32_t index,
   return NUTS_OK;
 }
 
+// y_obs [N] of a node in its evaluation order, stream-ordered: the node's own vector (GLM, mixture), or *y_own, which the caller
+// has allocated with N doubles for a factor or the logit rows (and frees)
+static const double* pp_y_obs(nuts_model* m, int kind, int index, int64_t N, double* y_own) {
+  const ModelDev& md = m->md;
+  const unsigned nblk = (unsigned)((N + LL_BLOCK - 1) / LL_BLOCK);
+  if (kind == NUTS_LL_FACTOR) {
+    // argument 0 of an observed factor is data: the position it is evaluated at (zeros) does not enter it
+    hipMemsetAsync(m->ll_q, 0, (size_t)std::max(md.n, 1) * sizeof(double), m->stream);
+    hipLaunchKernelGGL(k_pp_factor_y, dim3(nblk), dim3(LL_BLOCK), 0, m->stream, md, (const double*)m->ll_q, index, y_own);
+    return y_own;
+  }
+  if (kind == NUTS_LL_LOGIT_ROWS) {
+    hipLaunchKernelGGL(k_pp_rows_y, dim3(nblk, 1), dim3(LL_BLOCK), 0, m->stream, md, (const double*)m->ll_par, WAVE * m->rows_rpl,
+                       md.lg.ga_gpw ? 1 : md.lg.ga_w, y_own);
+    return y_own;
+  }
+  return kind == NUTS_LL_GLM ? md.glm.y : md.mix.y;
+}
+
 struct nuts_ppc {
   nuts_model* m;
   int32_t kind, index;
@@ -2729,17 +2769,9 @@ extern "C" nuts_ppc* nuts_ppc_create(nuts_model* m, int32_t kind, int32_t index,
     ppc_free(p);
     return nullptr;
   }
-  const ModelDev& md = m->md;
   const unsigned nblk = (unsigned)p->nblk;
   if (N > 0) {
-    if (kind == NUTS_LL_FACTOR) {
-      // argument 0 of an observed factor is data: the position it is evaluated at (zeros) does not enter it
-      hipMemsetAsync(m->ll_q, 0, (size_t)std::max(md.n, 1) * sizeof(double), m->stream);
-      hipLaunchKernelGGL(k_pp_factor_y, dim3(nblk), dim3(LL_BLOCK), 0, m->stream, md, (const double*)m->ll_q, index, p->y_own);
-    } else if (kind == NUTS_LL_LOGIT_ROWS)
-      hipLaunchKernelGGL(k_pp_rows_y, dim3(nblk, 1), dim3(LL_BLOCK), 0, m->stream, md, (const double*)m->ll_par, WAVE * m->rows_rpl,
-                         md.lg.ga_gpw ? 1 : md.lg.ga_w, p->y_own);
-    p->y_obs = own ? p->y_own : (kind == NUTS_LL_GLM ? md.glm.y : md.mix.y);
+    p->y_obs = pp_y_obs(m, kind, index, N, p->y_own);
     hipLaunchKernelGGL(k_ppc_init, dim3(nblk), dim3(LL_BLOCK), 0, m->stream, N, p->acc);
     // T of the observed data: the same partials, the same reduce
     hipLaunchKernelGGL(k_ppc_fold, dim3(nblk), dim3(LL_BLOCK), 0, m->stream, p->y_obs, 1, N, (int64_t)0, p->y_obs, (double*)nullptr, p->part);
@@ -2815,6 +2847,120 @@ extern "C" void nuts_ppc_destroy(nuts_ppc* p) {
   hipStreamSynchronize(p->m->stream);
   p->m->n_waic--;
   ppc_free(p);
+}
+
+// ---- LOO predictive checks: the second pass (psis.h psis_fit / psis_weight, loo_pit_kernel.h) ----------------------
+struct nuts_loo_pit {
+  nuts_model* m;         // (its own copy: destroy does not touch p)
+  nuts_psis* p;          // borrowed: keep, fit, kind, index, n_draws
+  uint64_t seed;
+  uint32_t tag;
+  int64_t N, count;
+  const double* y_obs;   // [N] in the node's evaluation order
+  double *y_own, *acc, *w;   // acc [6][N]: sum w, sum w^2, sum w [<], sum w [==], mean, M2; w [LL_B][N]: the batch's weights
+};
+
+static void loo_pit_free(nuts_loo_pit* h) {
+  for (double* d : {h->y_own, h->acc, h->w}) if (d) hipFree(d);
+  delete h;
+}
+
+extern "C" nuts_loo_pit* nuts_loo_pit_create(nuts_psis* p, uint64_t seed) {
+  if (!p) { g_err = "null argument"; return nullptr; }
+  nuts_model* m = p->m;
+  int64_t N = 0;
+  uint32_t tag = 0;
+  if (pp_check(m, p->kind, p->index, &N, &tag)) return nullptr;
+  if (p->count != p->n_draws) {
+    g_err = "nuts_loo_pit_create: " + std::to_string(p->count) + " of " + std::to_string(p->n_draws) + " draws of the first pass are in";
+    return nullptr;
+  }
+  if (ll_ensure(m, p->kind, N)) return nullptr;
+  if (psis_ensure_fit(p)) return nullptr;
+  auto* h = new nuts_loo_pit{m, p, seed, tag, N, 0, nullptr, nullptr, nullptr, nullptr};
+  const size_t n1 = (size_t)std::max<int64_t>(N, 1);
+  const bool own = p->kind == NUTS_LL_FACTOR || p->kind == NUTS_LL_LOGIT_ROWS;
+  if ((own && hipMalloc((void**)&h->y_own, n1 * sizeof(double)) != hipSuccess) || hipMalloc((void**)&h->acc, 6 * n1 * sizeof(double)) != hipSuccess ||
+      hipMalloc((void**)&h->w, LL_B * n1 * sizeof(double)) != hipSuccess) {
+    (void)hipGetLastError();
+    g_err = "LOO-PIT state: device allocation of " + std::to_string((6 + LL_B + (own ? 1 : 0)) * n1 * sizeof(double)) + " bytes failed";
+    loo_pit_free(h);
+    return nullptr;
+  }
+  if (N > 0) {
+    h->y_obs = pp_y_obs(m, p->kind, p->index, N, h->y_own);
+    hipLaunchKernelGGL(k_loo_init, dim3((unsigned)((N + LL_BLOCK - 1) / LL_BLOCK)), dim3(LL_BLOCK), 0, m->stream, N, h->acc);
+  }
+  if (hipStreamSynchronize(m->stream) != hipSuccess || hipGetLastError() != hipSuccess) {
+    g_err = "LOO-PIT: building the fit and y_obs failed";
+    loo_pit_free(h);
+    return nullptr;
+  }
+  m->n_waic++;
+  return h;
+}
+
+extern "C" int nuts_loo_pit_update(nuts_loo_pit* h, const double* q, int64_t S, int64_t draw0) {
+  if (!h || S < 0 || (S > 0 && !q)) { g_err = "null argument"; return NUTS_E_ARG; }
+  nuts_psis* p = h->p;
+  nuts_model* m = p->m;
+  int64_t N = 0;
+  uint32_t tag = 0;
+  if (const int rc = pp_check(m, p->kind, p->index, &N, &tag)) return rc;
+  if (const int rc = pp_draw_range(draw0, S)) return rc;
+  if (h->count + S > p->n_draws) {
+    g_err = "nuts_loo_pit_update: " + std::to_string(h->count) + " + " + std::to_string(S) + " draws exceed the " + std::to_string(p->n_draws) +
+            " of the first pass";
+    return NUTS_E_ARG;
+  }
+  if (const int rc = ll_ensure(m, p->kind, N)) return rc;
+  const int B = ll_batch();
+  const unsigned nblk = (unsigned)((N + LL_BLOCK - 1) / LL_BLOCK);
+  for (int64_t s0 = 0; s0 < S; s0 += B) {
+    const int nb = (int)std::min<int64_t>(B, S - s0);
+    const double* qb = q + (size_t)s0 * m->md.n;
+    if (const int rc = ll_eval_batch(m, p->kind, p->index, qb, nb, N, B)) return rc;
+    // the weights are parked before the replicates overwrite the model's one stage
+    if (N > 0)
+      hipLaunchKernelGGL(k_loo_weight, dim3(nblk, nb), dim3(LL_BLOCK), 0, m->stream, (const double*)m->ll_stage, N, (const double*)p->fit,
+                         (const double*)p->keep, h->w);
+    if (const int rc = pp_eval_batch(m, p->kind, p->index, qb, nb, N, B, PPAddr{pp_key(h->seed), tag, (uint32_t)(draw0 + s0)})) return rc;
+    if (N > 0)
+      hipLaunchKernelGGL(k_loo_fold, dim3(nblk), dim3(LL_BLOCK), 0, m->stream, (const double*)h->w, (const double*)m->ll_stage, nb, N, h->y_obs, h->acc);
+    h->count += nb;
+  }
+  HIPCHK(hipStreamSynchronize(m->stream));   // (the caller may reuse q)
+  HIPCHK(hipGetLastError());
+  return NUTS_OK;
+}
+
+extern "C" int nuts_loo_pit_read(nuts_loo_pit* h, double* p_lt, double* p_eq, double* mean, double* var, double* sum_w, double* sum_w2,
+                                 int64_t* n_draws) {
+  if (!h) { g_err = "null argument"; return NUTS_E_ARG; }
+  if (n_draws) *n_draws = h->count;
+  const int64_t N = h->N;
+  if (N == 0 || (!p_lt && !p_eq && !mean && !var && !sum_w && !sum_w2)) return NUTS_OK;
+  HIPCHK(hipStreamSynchronize(h->p->m->stream));
+  std::vector<double> acc(6 * (size_t)N), state((size_t)N);
+  HIPCHK(hipMemcpy(acc.data(), h->acc, 6 * (size_t)N * sizeof(double), hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(state.data(), h->p->fit + 6 * (size_t)N, (size_t)N * sizeof(double), hipMemcpyDeviceToHost));
+  double* dst[6] = {sum_w, sum_w2, p_lt, p_eq, mean, var};
+  for (int k = 0; k < 6; ++k) {
+    if (!dst[k]) continue;
+    for (int64_t i = 0; i < N; ++i) {
+      const double a = acc[(size_t)k * N + i];
+      // a degenerate or poisoned fit has no weights; var = M2 / sum w, the weighted population variance
+      dst[k][i] = state[i] != (double)PSIS_FIT_OK ? NAN : (k == 5 ? a / acc[i] : a);
+    }
+  }
+  return NUTS_OK;
+}
+
+extern "C" void nuts_loo_pit_destroy(nuts_loo_pit* h) {
+  if (!h) return;
+  hipStreamSynchronize(h->m->stream);
+  h->m->n_waic--;
+  loo_pit_free(h);
 }
 
 // ---- convergence summary of a trace (summary.h, summary_kernel.h) ---------------------------------------------------

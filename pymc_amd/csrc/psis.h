@@ -11,6 +11,10 @@
 //   R = r_rest exp(m_rest - c).
 // A value rejected by or evicted from the kept set is at most the (M + 1)-th largest ratio, so it is never in the tail: R is summed
 // as values leave and nothing is ever subtracted from a total.
+//
+// psis_fit returns the same fit as a record (PsisFit) and psis_weight the normalised smoothed weight of one draw from it: what the
+// second pass of LOO-PIT (loo_pit_kernel.h) weights the replicates of each draw with, held to tests/loo_pit_reference.py by
+// tests/loo_pit_check.cpp / tests/test_loo_pit_host.py.
 #pragma once
 #include <float.h>
 #include <math.h>
@@ -80,13 +84,25 @@ PSIS_HD double psis_gpinv(double p, double k, double s) {
 
 struct PsisOut { double khat, elpd; };
 
+// The fit of one observation as a record: everything the smoothed weight of ANY of its draws follows from (psis_weight), so that a
+// second pass over the draws can weight them one by one.  logden = log(R + sum_{kept, not tail} exp t + sum_tail exp sm), the
+// normaliser of the identity above.
+#define PSIS_FIT_OK 0
+#define PSIS_FIT_DEGENERATE 1   // keep[0] = -inf: the left-out density is 0, elpd = -inf
+#define PSIS_FIT_POISONED 2     // r_rest NaN: a NaN or +inf value
+#define PSIS_FIT_FIELDS 7       // c, xc, tl, khat, sigma, logden, state (the order of a [PSIS_FIT_FIELDS][N] block)
+struct PsisFit { double c, xc, khat, sigma, logden; int tl, state; };
+
 // keep: the column of K1 = psis_tail_len(S, reff) + 1 values after all S draws (reff enters through K1 alone; the caller passes the
 // K1 the column was allocated with); work[j * wstride], j < PSIS_WORK: the fit's candidates (registers, LDS or the stack).
-PSIS_HD PsisOut psis_finish(const double* keep, int64_t stride, int K1, double m_rest, double r_rest, int64_t S, double* work, int wstride) {
-  PsisOut o;
-  if (r_rest != r_rest) { o.khat = NAN; o.elpd = NAN; return o; }                     // a NaN or +inf value
+// num = sum_tail exp(sm - t), the one term of elpd_loo_i that is not part of the record.
+PSIS_HD PsisFit psis_fit_num(const double* keep, int64_t stride, int K1, double m_rest, double r_rest, double* work, int wstride, double& num_out) {
+  PsisFit f;
+  f.c = NAN; f.xc = NAN; f.khat = NAN; f.sigma = NAN; f.logden = NAN; f.tl = 0; f.state = PSIS_FIT_OK;
+  num_out = NAN;
+  if (r_rest != r_rest) { f.state = PSIS_FIT_POISONED; return f; }                          // a NaN or +inf value
   const double k0 = keep[0];
-  if (k0 == -INFINITY) { o.khat = INFINITY; o.elpd = -INFINITY; return o; }           // the left-out density is 0
+  if (k0 == -INFINITY) { f.khat = INFINITY; f.state = PSIS_FIT_DEGENERATE; return f; }      // the left-out density is 0
   const double c = -k0;
 #define PSIS_T(j) (-keep[(int64_t)(j) * stride] - c)
   const double xc = fmax(PSIS_T(K1 - 1), log(DBL_MIN)), exc = exp(xc);
@@ -143,7 +159,62 @@ PSIS_HD PsisOut psis_finish(const double* keep, int64_t stride, int K1, double m
   }
 #undef PSIS_T
   const double R = m_rest == -INFINITY ? 0.0 : r_rest * exp(m_rest - c);
-  o.khat = khat;
-  o.elpd = -c + log((double)(S - tl) + num) - log(R + den_kept + den_tail);
+  f.c = c; f.xc = xc; f.tl = tl; f.khat = khat; f.sigma = sigma;
+  f.logden = log(R + den_kept + den_tail);
+  num_out = num;
+  return f;
+}
+
+PSIS_HD PsisFit psis_fit(const double* keep, int64_t stride, int K1, double m_rest, double r_rest, int64_t S, double* work, int wstride) {
+  (void)S;   // (the record does not depend on it: S enters elpd_loo_i alone)
+  double num;
+  return psis_fit_num(keep, stride, K1, m_rest, r_rest, work, wstride, num);
+}
+
+PSIS_HD PsisOut psis_finish(const double* keep, int64_t stride, int K1, double m_rest, double r_rest, int64_t S, double* work, int wstride) {
+  PsisOut o;
+  double num;
+  const PsisFit f = psis_fit_num(keep, stride, K1, m_rest, r_rest, work, wstride, num);
+  if (f.state == PSIS_FIT_POISONED) { o.khat = NAN; o.elpd = NAN; return o; }
+  if (f.state == PSIS_FIT_DEGENERATE) { o.khat = INFINITY; o.elpd = -INFINITY; return o; }
+  o.khat = f.khat;
+  o.elpd = -f.c + log((double)(S - f.tl) + num) - f.logden;
   return o;
+}
+
+// The smoothed value of rank j < tl of the tail, exactly as psis_fit_num forms it; t_j = -keep[j] - c.
+PSIS_HD double psis_smoothed(const PsisFit& f, double t_j, int j) {
+  if (!(f.khat - f.khat == 0.0)) return t_j;   // nothing is smoothed
+  double sm = log(psis_gpinv(((double)(f.tl - 1 - j) + 0.5) / (double)f.tl, f.khat, f.sigma) + exp(f.xc));
+  if (sm > 0.0) sm = 0.0;
+  return sm;
+}
+
+// The normalised Pareto-smoothed weight of a draw whose log-likelihood is v, from the record and the sorted column: the weights of
+// all S draws of the first pass sum to 1.  A draw outside the tail (t = -v - c <= xc) keeps its raw weight exp(t - logden).  A draw
+// of the tail takes the smoothed value of its RANK, which is its position in keep[0 .. tl).
+//
+// Ties.  ArviZ hands tied ratios different smoothed weights in the order the draws happen to be stored (a stable argsort), so its
+// result depends on the order of the trace.  Here a value that occupies the ranks [j0, j1) takes the ARITHMETIC MEAN of their
+// weights: the sum of the weights stays 1, the result does not depend on the order of the draws, and it is ArviZ's whenever a
+// value occurs once.  A v that is not in the column (the caller streamed draws the first pass did not see) takes the weight of its
+// insertion rank; the weights then no longer sum to 1, which is how the misuse is noticed.
+PSIS_HD double psis_weight(const PsisFit& f, const double* keep, int64_t stride, double v) {
+  if (f.state != PSIS_FIT_OK) return NAN;
+  const double t = -v - f.c;
+  if (!(t > f.xc) || f.tl == 0) return exp(t - f.logden);   // (a NaN value stays NaN; an empty tail has no rank to give)
+  int j0 = 0, n = f.tl;                        // lower bound: the first rank whose value is not below v
+  while (n > 0) {
+    const int h = n >> 1;
+    if (keep[(int64_t)(j0 + h) * stride] < v) { j0 += h + 1; n -= h + 1; } else n = h;
+  }
+  int j1 = j0;
+  while (j1 < f.tl && keep[(int64_t)j1 * stride] == v) ++j1;
+  if (j1 == j0) {                              // not found: the insertion rank
+    if (j0 >= f.tl) j0 = f.tl - 1;
+    j1 = j0 + 1;
+  }
+  double s = 0.0;
+  for (int j = j0; j < j1; ++j) s += exp(psis_smoothed(f, -keep[(int64_t)j * stride] - f.c, j) - f.logden);
+  return j1 - j0 == 1 ? s : s / (double)(j1 - j0);
 }

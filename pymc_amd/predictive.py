@@ -4,7 +4,9 @@
 `az.plot_bpv` then look at per-observation predictive means and p-values and at the distribution of test statistics T(y_rep) against
 T(y).  Here the replicates come from the engine (csrc/predictive.h, csrc/predictive_kernel.h): `sample_posterior_predictive`
 returns the arrays, `ppc` accumulates the per-observation and per-draw summaries on the device while the draws stream by and never
-holds the (draws x observations) matrix -- the models this engine exists for have 10^6 observations.
+holds the (draws x observations) matrix -- the models this engine exists for have 10^6 observations.  `loo_pit` (`az.loo_pit`, the LOO
+predictive mean and sd) weights the replicates by the Pareto-smoothed leave-one-out weights in a second streamed pass
+(csrc/psis.h psis_fit / psis_weight, csrc/loo_pit_kernel.h).
 
 The generator is counter-based: the value of (draw s, observation i) of a variable depends on (seed, variable, s, i) and on the
 variable's parameters at draw s, never on how the draws were batched or split over calls.  s is the GLOBAL draw index: draw d of the model's
@@ -148,3 +150,81 @@ def ppc(model, draws, *, var_name: Optional[str] = None, random_seed=0, pointwis
             f.close()
     mean_i, var_i, n_lt, n_eq = (loglik.caller_order(spec, node[1], a) for a in (mean_i, var_i, n_lt, n_eq))
     return ppc_from_accumulators(mean_i, var_i, n_lt, n_eq, T, T_obs, n_draws, pointwise=pointwise)
+
+
+def loo_pit_from_accumulators(p_lt, p_eq, mean, var, sum_w, sum_w2, elpd_loo_i, khat_i, lppd_i, n_draws: int, pointwise: bool = True) -> dict:
+    """The LOO predictive checks of N observations from the two streamed passes over S = `n_draws` pooled draws: the first pass's
+    PSIS results (`loglik.loo_from_pointwise`, whose keys are all returned) and the second pass's weighted sums.
+
+    loo_pit = p_lt + p_eq is ArviZ's `loo_pit` (the weight of y_rep <= y); loo_pit_mid = p_lt + p_eq / 2 is the mid-p value for
+    discrete data, the LOO counterpart of `ppc`'s p_i; loo_mean and loo_sd are the LOO predictive mean and standard deviation
+    (population, weighted); ess = 1 / sum w^2 the effective sample size of the weights; sum_w is 1 after a complete second pass.
+    An observation whose fit is degenerate (ll = -inf at a draw) or poisoned (a NaN or +inf value) has NaN in all of them.
+
+    Raises ValueError when an observation with a finite elpd_loo_i has |sum_w - 1| > 1e-9: the second pass streamed other draws
+    than the first, or not all of them."""
+    p_lt, p_eq, mean, var, sum_w, sum_w2 = (np.asarray(a, dtype="float64") for a in (p_lt, p_eq, mean, var, sum_w, sum_w2))
+    ok = np.isfinite(np.asarray(elpd_loo_i, dtype="float64"))
+    if np.any(~(np.abs(sum_w[ok] - 1.0) <= 1e-9)):
+        raise ValueError("the second pass did not see the draws of the first")
+    out = loglik.loo_from_pointwise(elpd_loo_i, khat_i, lppd_i, n_draws, pointwise=pointwise)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        out.update({
+            "loo_pit": p_lt + p_eq,
+            "loo_pit_mid": p_lt + 0.5 * p_eq,
+            "p_lt": p_lt,
+            "p_eq": p_eq,
+            "loo_mean": mean,
+            "loo_sd": np.sqrt(var),
+            "ess": 1.0 / sum_w2,
+            "sum_w": sum_w,
+        })
+    return out
+
+
+def loo_pit(model, draws, *, var_name: Optional[str] = None, reff: float = 1.0, random_seed=0, chain_ids=None, pointwise: bool = True,
+            device: Optional[int] = None, func=None) -> dict:
+    """`az.loo_pit` and the LOO predictive mean and sd of one observed variable, streamed: a first pass over the draws builds the
+    PSIS state (`loglik.loo`), a second weights each draw's replicate by its Pareto-smoothed leave-one-out weight and folds per
+    observation (see `loo_pit_from_accumulators`).  Neither the log-likelihood, the replicate nor the weight matrix
+    (draws x observations) is ever formed.  The chains are pooled in chain order; the replicates are those
+    `sample_posterior_predictive` returns under the same `random_seed` and `chain_ids`.  Arrays are in the order the observations
+    were passed.  `pointwise=False` drops `loo_i` and `pareto_k` (as `loglik.loo` does), not the LOO-PIT arrays.
+
+    Tied log-likelihood values of an observation share the mean of the weights of the ranks they occupy: the result does not depend
+    on the order of the draws (ArviZ's does; the two agree when no value repeats)."""
+    spec = loglik._spec_of(model)
+    nodes = ms.observed_nodes(spec)
+    why = loglik.refusal(spec, [])
+    if why:
+        raise ValueError("posterior predictive refused: " + why)
+    if not nodes:
+        raise ValueError("the model has no observed variable")
+    if var_name is None and len(nodes) > 1:
+        raise TypeError(f"Found several observed variables {[nd[0] for nd in nodes]}, var_name cannot be None")
+    node = _nodes_or_refuse(spec, var_name)[0]
+    q = loglik._draws_array(draws, spec.n)
+    ids = _chain_ids(draws, chain_ids, q.shape[0])
+    n_draws = q.shape[0] * q.shape[1]
+    f, own = loglik._function(spec, device, func)
+    try:
+        first = f.psis_accumulator(node[0], n_draws, reff=reff, node=(node[1], node[2]))
+        try:
+            for c in range(q.shape[0]):
+                first.update(q[c])
+            elpd_i, khat, lppd_i, _ = first.read()
+            second = f.loo_pit_accumulator(first, seed=random_seed)
+            try:
+                for k, c in enumerate(ids):
+                    second.update(q[k], draw0=c * q.shape[1])
+                cols = second.read()[:6]
+            finally:
+                second.close()
+        finally:
+            first.close()
+    finally:
+        if own:
+            f.close()
+    cols = [loglik.caller_order(spec, node[1], a) for a in cols]
+    elpd_i, khat, lppd_i = (loglik.caller_order(spec, node[1], a) for a in (elpd_i, khat, lppd_i))
+    return loo_pit_from_accumulators(*cols, elpd_i, khat, lppd_i, n_draws, pointwise=pointwise)

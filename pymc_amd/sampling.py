@@ -548,6 +548,7 @@ def sample(
     log_likelihood: bool = False,
     posterior_predictive: bool = False,
     summary: bool = False,
+    loo_pit: bool = False,
     **step_kwargs,
 ):
     """Reduced `pm.sample` (mcmc.py:620-1190) returning raw arrays (and, with ``return_multitrace=True``, the reference's
@@ -594,6 +595,11 @@ def sample(
     "hdi_hi": ..., "mcse_mean": ..., "mcse_sd": ..., "ess_bulk": ..., "ess_tail": ..., "r_hat": ...} with one row per element of every
     variable, computed on the device (pymc_amd/summary.py) from the draws the result holds after the gather; a rank left with no
     draws gets none.
+
+    ``loo_pit`` (`az.loo_pit` and the LOO predictive mean / sd of the finished trace): ``result["loo_pit"]`` = {observed variable:
+    the dict of `pymc_amd.predictive.loo_pit`} from two streamed passes over the draws the result holds, with the key and the draw
+    numbering of ``posterior_predictive``; a rank left with no draws gets none.  Refused before sampling where
+    ``posterior_predictive`` is.
     """
     rank, world, local = _dist_info()
     from pymc_amd.lowering import as_model_spec
@@ -611,6 +617,12 @@ def sample(
         why = pp_refusal(spec)
         if why:
             raise ValueError("posterior_predictive=True refused: " + why)
+    if loo_pit:
+        from pymc_amd.predictive import refusal as pp_refusal
+
+        why = pp_refusal(spec)
+        if why:
+            raise ValueError("loo_pit=True refused: " + why)
     if device is None and world > 1:
         device = local
     # mcmc.py:907-908 -- every rank derives ALL chain generators so chain c is the same stream on any layout
@@ -870,6 +882,14 @@ def sample(
         f = getattr(step, "_logp_dlogp_func", None)
         result["posterior_predictive"] = sample_posterior_predictive(spec, result["draws"], random_seed=seed_from(random_seed), device=device, chain_ids=result["chains"],
                                                                      func=f if hasattr(f, "posterior_predictive") else None)
+    if loo_pit and result["draws"] is not None and np.shape(result["draws"])[0] > 0:
+        from pymc_amd.model_spec import observed_nodes
+        from pymc_amd.predictive import loo_pit as loo_pit_of_trace, seed_from
+
+        f = getattr(step, "_logp_dlogp_func", None)
+        result["loo_pit"] = {nd[0]: loo_pit_of_trace(spec, result["draws"], var_name=nd[0], random_seed=seed_from(random_seed), chain_ids=result["chains"],
+                                                     device=device, func=f if hasattr(f, "loo_pit_accumulator") else None)
+                             for nd in observed_nodes(spec)}
     if summary and result["draws"] is not None and np.shape(result["draws"])[0] > 0:
         from pymc_amd.summary import summary as summarize_trace
 

@@ -273,6 +273,13 @@ class DeviceValueGradFunction:
         kind, index = self._ll_node(name, node)
         return PpcAccumulator(self, kind, index, seed)
 
+    def loo_pit_accumulator(self, psis_accumulator: "PsisAccumulator", seed: int = 0) -> "LooPitAccumulator":
+        """Device-resident LOO predictive checks of the observed variable of `psis_accumulator`, which must hold all of its draws:
+        the second pass over them (`nuts_loo_pit_*`)."""
+        if psis_accumulator._func is not self:
+            raise ValueError("the PSIS accumulator belongs to another function")
+        return LooPitAccumulator(psis_accumulator, seed)
+
     def time_kernels(self, q, reps=20):
         ms_tot, ms_dom = C.c_double(), C.c_double()
         q = np.ascontiguousarray(q, dtype="float64")
@@ -428,6 +435,54 @@ class PpcAccumulator:
     def close(self):
         if getattr(self, "_handle", None):
             _lib.load().nuts_ppc_destroy(self._handle)
+            self._handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class LooPitAccumulator:
+    """`nuts_loo_pit`: the second pass over the draws of a finished `PsisAccumulator` (which it borrows and keeps alive).  Per
+    observation the sums of the Pareto-smoothed weights w, of w^2, of w over the replicates below / at the observed value, and the
+    weighted mean and variance of the replicates; `update(q [S, n], draw0)` in any split, the replicate of a draw addressed by its
+    global number `draw0` + position."""
+
+    def __init__(self, psis: PsisAccumulator, seed: int = 0):
+        lib = _lib.load()
+        self._psis = psis      # (the handle borrows its sorted column and must not outlive it)
+        self._func = psis._func
+        self.size = psis.size
+        if not getattr(psis, "_handle", None):
+            raise ValueError("nuts_loo_pit_create: the PSIS accumulator is closed")
+        self._handle = lib.nuts_loo_pit_create(psis._handle, int(seed) & 0xFFFFFFFFFFFFFFFF)
+        if not self._handle:
+            raise ValueError(f"nuts_loo_pit_create: {_lib.last_error()}")
+
+    def _live(self):
+        if not getattr(self._psis, "_handle", None):
+            raise ValueError("the PSIS accumulator this pass reads from was closed")
+
+    def update(self, q, draw0: int = 0) -> None:
+        self._live()
+        q = np.ascontiguousarray(np.asarray(q, dtype="float64").reshape(-1, self._func.n))
+        _lib.check(_lib.load().nuts_loo_pit_update(self._handle, _lib.dptr(q), q.shape[0], int(draw0)), "nuts_loo_pit_update")
+
+    def read(self):
+        """(p_lt, p_eq, mean, var, sum_w, sum_w2, draws so far); NaN in every column where the fit is degenerate or poisoned"""
+        self._live()
+        p_lt, p_eq, mean, var, sum_w, sum_w2 = (np.empty(self.size) for _ in range(6))
+        n = C.c_int64()
+        rc = _lib.load().nuts_loo_pit_read(self._handle, _lib.dptr(p_lt), _lib.dptr(p_eq), _lib.dptr(mean), _lib.dptr(var), _lib.dptr(sum_w),
+                                           _lib.dptr(sum_w2), C.byref(n))
+        _lib.check(rc, "nuts_loo_pit_read")
+        return p_lt, p_eq, mean, var, sum_w, sum_w2, n.value
+
+    def close(self):
+        if getattr(self, "_handle", None):
+            _lib.load().nuts_loo_pit_destroy(self._handle)
             self._handle = None
 
     def __del__(self):

@@ -2,6 +2,7 @@
 
     python tools/loglik_bench.py [--draws 64] [--loo-draws 1000] [--out profiles/loglik_bench.json] [--small]
     python tools/loglik_bench.py --predictive [--draws 64] [--out profiles/predictive_bench.json] [--small]
+    python tools/loglik_bench.py --loo-pit [--loo-draws 1000] [--out profiles/loo_pit_bench.json] [--small]
 
 At configs[3]'s GLM shape (1 M rows x 512 covariates, Bernoulli) and at C2-L (hierarchical-logit rows, 4 992 000 rows), on one GPU
 in one process:
@@ -22,6 +23,13 @@ streaming checks: nothing but the draws crosses PCIe) and of `nuts_model_predict
 with `nuts_waic_update` over the same draws in the same run next to them, and their ratios to it.  By the shapes a draw of the
 predictive path moves what WAIC's moves (one read of X per batch of B) plus 16 N bytes: the row pass stores eta, k_pp_draw reads
 it and stores the variate in its place.
+
+`--loo-pit` runs the LOO-PIT leg INSTEAD (`predictive.loo_pit`): over `--loo-draws` draws around the initial point, microseconds per
+draw of the SECOND pass (`nuts_loo_pit_update`: per batch the log-likelihood, the weights, the replicates, the fold), with
+`nuts_waic_update`, `nuts_psis_update` (the first pass) and `nuts_ppc_update` over the same draws in the same run next to it, the
+one-off `nuts_loo_pit_create` (k_psis_fit over every observation) and the read.  By the shapes a second-pass draw should cost about
+one WAIC draw plus one predictive draw plus 24 N bytes (the weight block written and read, the accumulators): the figure reported
+as `loo_pit_over_waic_plus_ppc`.
 
 Reported per shape: microseconds per draw, the ratio to the parent's pass, and the bytes a draw moves by the shapes
 (GLM: 8 N P / B + 8 N; rows: 8 N per draw written, X read once per draw: 8 N D_stored + N).  The claim to check is "a batch of B
@@ -118,6 +126,57 @@ def measure_predictive(spec, name, draws, seed=0):
     return out
 
 
+def measure_loo_pit(spec, name, draws, seed=1):
+    from pymc_amd.value_grad import DeviceValueGradFunction
+
+    f = DeviceValueGradFunction(spec, device=0)
+    q = np.random.default_rng(seed).normal(size=(draws, spec.n)) * 0.1
+    out = {"loo_draws": draws}
+    try:
+        out["batch"] = int(f.model_scalar("loglik_batch"))
+
+        def waic_once():
+            acc = f.waic_accumulator(name)
+            acc.update(q)
+            acc.close()
+
+        def ppc_once():
+            acc = f.ppc_accumulator(name, seed=1)
+            acc.update(q)
+            acc.close()
+
+        waic_once()                                        # warm-up: buffers, first launches
+        out["waic_us_per_draw"] = 1e6 * _wall(waic_once) / draws
+        ppc_once()
+        out["ppc_us_per_draw"] = 1e6 * _wall(ppc_once) / draws
+        first = f.psis_accumulator(name, draws)
+        try:
+            out["psis_us_per_draw"] = 1e6 * _wall(lambda: first.update(q)) / draws
+            t0 = time.perf_counter()
+            second = f.loo_pit_accumulator(first, seed=1)
+            out["loo_pit_create_ms"] = 1e3 * (time.perf_counter() - t0)
+            try:
+                out["loo_pit_us_per_draw"] = 1e6 * _wall(lambda: second.update(q)) / draws
+                t0 = time.perf_counter()
+                p_lt, p_eq, mean, var, sum_w, sum_w2, n = second.read()
+                out["loo_pit_read_ms"] = 1e3 * (time.perf_counter() - t0)
+            finally:
+                second.close()
+            ok = ~np.isnan(sum_w)
+            out["observations_with_a_fit"] = int(ok.sum())
+            out["sum_w_max_abs_error"] = float(np.max(np.abs(sum_w[ok] - 1.0))) if ok.any() else None
+            out["ess_min"] = float(np.min(1.0 / sum_w2[ok])) if ok.any() else None
+            out["loo_pit_state_bytes"] = 8 * (7 + 6 + out["batch"]) * int(sum_w.size)
+        finally:
+            first.close()
+    finally:
+        f.close()
+    out["loo_pit_over_waic"] = out["loo_pit_us_per_draw"] / out["waic_us_per_draw"]
+    out["loo_pit_over_waic_plus_ppc"] = out["loo_pit_us_per_draw"] / (out["waic_us_per_draw"] + out["ppc_us_per_draw"])
+    out["loo_pit_over_psis"] = out["loo_pit_us_per_draw"] / out["psis_us_per_draw"]
+    return out
+
+
 def measure(spec, name, draws, seed=0, loo_draws=0):
     from pymc_amd import _lib
     from pymc_amd.value_grad import DeviceValueGradFunction
@@ -167,14 +226,32 @@ def main():
     ap.add_argument("--out", default=None, help="default: profiles/loglik_bench.json (profiles/predictive_bench.json with --predictive)")
     ap.add_argument("--small", action="store_true")
     ap.add_argument("--predictive", action="store_true", help="the posterior-predictive leg instead of the log-likelihood legs")
+    ap.add_argument("--loo-pit", action="store_true", help="the LOO-PIT leg (the second pass) instead of the log-likelihood legs")
     a = ap.parse_args()
     from pymc_amd import models
 
-    a.out = a.out or os.path.join(ROOT, "profiles", "predictive_bench.json" if a.predictive else "loglik_bench.json")
+    a.out = a.out or os.path.join(ROOT, "profiles", "loo_pit_bench.json" if a.loo_pit else "predictive_bench.json" if a.predictive else "loglik_bench.json")
     div = 16 if a.small else 1
     res = {"draws": a.draws, "loo_draws": a.loo_draws, "small": bool(a.small)}
     N, P = 1_000_000 // div, 512
     G, D, rpg = 1248, 8, 4000 // div
+    if a.loo_pit:
+        res = {"loo_draws": a.loo_draws, "small": bool(a.small)}
+        r = measure_loo_pit(models.glm_nuts(N=N, P=P, family="bernoulli"), "y", a.loo_draws)
+        r.update(N=N, P=P, bytes_per_draw_waic=8 * N * P / r["batch"] + 8 * N, bytes_per_draw_ppc=8 * N * P / r["batch"] + 8 * N + 16 * N)
+        r["bytes_per_draw_loo_pit"] = r["bytes_per_draw_waic"] + r["bytes_per_draw_ppc"] + 24 * N
+        res["glm"] = r
+        print(json.dumps({"glm": r}), flush=True)
+        Nr = G * rpg
+        r = measure_loo_pit(models.hier_logit(G=G, D=D, rows_per_group=rpg), "y", a.loo_draws)
+        r.update(N=Nr, D=D, bytes_per_draw_waic=8 * Nr * (D - 1) + Nr + 8 * Nr, bytes_per_draw_ppc=8 * Nr * (D - 1) + Nr + 8 * Nr + 16 * Nr)
+        r["bytes_per_draw_loo_pit"] = r["bytes_per_draw_waic"] + r["bytes_per_draw_ppc"] + 24 * Nr
+        res["c2l"] = r
+        print(json.dumps({"c2l": r}), flush=True)
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as fh:
+            json.dump(res, fh, indent=1, sort_keys=True)
+        return
     if a.predictive:
         res = {"draws": a.draws, "small": bool(a.small)}
         r = measure_predictive(models.glm_nuts(N=N, P=P, family="bernoulli"), "y", a.draws)
