@@ -445,6 +445,40 @@ int64_t nuts_summary_max_draws(void);
 int nuts_summary(const double *x /* host [C][N][P] */, int64_t C, int64_t N, int64_t P, double hdi_prob,
                  double *out /* host [NUTS_SUMMARY_COLS][P] */);
 
+/* ---- model comparison: `az.compare` on the log scale ----------------------------------------------------------------------------------
+ * K models over the same N observations, each given by its pointwise elpd (loo_i of nuts_psis_read, waic_i of nuts_waic_read): the
+ * elpd of every model with its standard error, the standard error of its difference to the best one, and the model weights by
+ * stacking (Yao, Vehtari, Simpson, Gelman 2018) or by pseudo-BMA with the Bayesian bootstrap.  pymc_amd/csrc/compare.h holds the
+ * definitions, the counter layout of the bootstrap's generator and the solver; DESIGN.md 4.21.  The state is 16 K N bytes on the
+ * current device (nuts_set_device); no model is needed.
+ *   nuts_compare_create:   NULL (text in nuts_last_error()) unless N >= 1 and 2 <= K <= NUTS_COMPARE_MAX_MODELS.
+ *   nuts_compare_set:      row k.  With `order`, elpd_i[j] belongs to observation order[j] (a permutation of 0 .. N - 1, e.g. the
+ *                          group-sorted order the logit rows are evaluated in).  A non-finite value is refused with the model and the
+ *                          smallest observation it occurs at -- PSIS gives -inf or NaN where a draw's density is 0, and a model
+ *                          with such an observation is not compared; a refused call leaves the row as it was.
+ *   nuts_compare_moments:  elpd_k = sum_i e_ik, se_k = sqrt(N var(e_.k)), dse_k = sqrt(N var(e_.best - e_.k)) (population variances,
+ *                          two passes), best = the first k of the largest elpd; dse[best] = 0.
+ *   nuts_compare_stacking: the weights maximising f(w) = sum_i log sum_k w_k exp(e_ik) over the simplex, objective = f(w), and the
+ *                          certificate kkt_gap = max_k (1 / N) sum_i exp(e_ik) / sum_l w_l exp(e_il) - 1 >= 0, which bounds
+ *                          f* - f(w) by N kkt_gap.  The solver stops at kkt_gap <= 1e-10 or after 64 passes over the observations,
+ *                          whichever comes first: `passes` = 64 with a larger gap says the cap was hit.
+ *   nuts_compare_bb:       b_samples (1 .. 65536) replicates of the Bayesian bootstrap under `seed`: z[b][k] = N sum_i a_bi e_ik with
+ *                          a_b. a Dirichlet(1, ..., 1) vector, w_k = mean_b softmax_k(z[b][.]), se_bb_k = the population standard
+ *                          deviation of z[.][k].  Replicate b depends on (seed, b) alone, not on b_samples.
+ * Every call needs all K rows set (NUTS_E_ARG otherwise).  The sums are added in one fixed order for a given number of workgroups:
+ * the option NUTS_COMPARE_WGS (0: chosen from N; the bootstrap uses at most 4096 of them, which bounds its partial sums at
+ * 4096 x 256 x (K + 1) doubles), read at every call.  The handle's memory lives on the device that was current at
+ * nuts_compare_create and the handle does not remember it: make that device current (nuts_set_device) before every later call, as
+ * for nuts_summary. */
+#define NUTS_COMPARE_MAX_MODELS 8
+typedef struct nuts_compare nuts_compare;
+nuts_compare *nuts_compare_create(int64_t N, int32_t K);
+int nuts_compare_set(nuts_compare *h, int32_t k, const double *elpd_i /* host [N] */, const int64_t *order /* NULL or host [N] */);
+int nuts_compare_moments(nuts_compare *h, double *elpd, double *se, double *dse, int32_t *best);   /* [K] each */
+int nuts_compare_stacking(nuts_compare *h, double *w, double *objective, double *kkt_gap, int32_t *passes);
+int nuts_compare_bb(nuts_compare *h, int64_t b_samples, uint64_t seed, double *w, double *se_bb, double *z /* NULL or host [b_samples][K] */);
+void nuts_compare_destroy(nuts_compare *h);
+
 /* ---- chain: replaces BaseHMC/NUTS + potential + step adaptation ------------- */
 /* NUTS_POT_FULL covers QuadPotentialFull and QuadPotentialFullInv (quadpotential.py:633-725): the caller passes
  * the dense covariance C (velocity = C p) and the matrix W with potential.random() = W z

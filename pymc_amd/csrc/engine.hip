@@ -28,6 +28,7 @@
 #include "predictive_kernel.h"
 #include "loo_pit_kernel.h"
 #include "summary_kernel.h"
+#include "compare_kernel.h"
 #include "nuts_mi355.h"
 #include "pcg64_stream.h"
 #include "advi.h"
@@ -3004,6 +3005,246 @@ extern "C" int nuts_summary(const double* x, int64_t C, int64_t N, int64_t P, do
   if (xt) hipFree(xt);
   if (res) hipFree(res);
   HIPCHK_RET(e, "nuts_summary", NUTS_E_HIP);
+  return NUTS_OK;
+}
+
+// ---- model comparison (compare.h, compare_kernel.h) -------------------------------------------------------------------
+// No model: K rows of N pointwise elpd values from the host.  Everything runs on the null stream, one call after the other; the host
+// reads a handful of sums per launch pair (K (K + 3) / 2 + 1 per stacking pass).
+static_assert(NUTS_COMPARE_MAX_MODELS == CMP_MAXK, "compare.h restates the model limit of nuts_mi355.h");
+struct nuts_compare {
+  int64_t N = 0;
+  int K = 0;
+  double *e = nullptr, *p = nullptr, *stage = nullptr, *part = nullptr, *out = nullptr;
+  size_t part_cap = 0, out_cap = 0;
+  bool set[CMP_MAXK] = {};
+  bool terms = false;
+  double sum_m = 0.0;
+};
+
+#define CMP_DISPATCH(K, ...)                                                                     \
+  switch (K) {                                                                                     \
+    case 2: { constexpr int KK = 2; __VA_ARGS__; } break;  case 3: { constexpr int KK = 3; __VA_ARGS__; } break; \
+    case 4: { constexpr int KK = 4; __VA_ARGS__; } break;  case 5: { constexpr int KK = 5; __VA_ARGS__; } break; \
+    case 6: { constexpr int KK = 6; __VA_ARGS__; } break;  case 7: { constexpr int KK = 7; __VA_ARGS__; } break; \
+    default: { constexpr int KK = 8; __VA_ARGS__; } break;                                                \
+  }
+
+// workgroups of the streaming kernels (`units` = ceil(N / CMP_BLOCK)) and of the bootstrap (`units` = its slabs): the option, or
+// as many as there is work for up to `cap`; the option itself is cut at `most` (the bootstrap's slots are workgroups x 256 x (K + 1)
+// doubles: 4096 workgroups bound them at 75 MB for K = 8)
+static int cmp_wgs(int64_t units, int cap, int most, int* out) {
+  const int opt = env_int("NUTS_COMPARE_WGS", 0);
+  if (opt < 0 || opt > 65535) { g_err = "NUTS_COMPARE_WGS must lie in 0 .. 65535 (0: chosen from N)"; return NUTS_E_ARG; }
+  *out = (int)std::max<int64_t>(1, std::min<int64_t>(units, opt > 0 ? std::min(opt, most) : cap));
+  return NUTS_OK;
+}
+
+static int cmp_reserve(nuts_compare* h, size_t part, size_t out) {
+  if (part > h->part_cap) {
+    if (h->part) hipFree(h->part);
+    h->part_cap = 0;
+    h->part = dev_alloc<double>(part);
+    if (!h->part) { g_err = "nuts_compare: out of device memory (partial sums)"; return NUTS_E_HIP; }
+    h->part_cap = part;
+  }
+  if (out > h->out_cap) {
+    if (h->out) hipFree(h->out);
+    h->out_cap = 0;
+    h->out = dev_alloc<double>(out);
+    if (!h->out) { g_err = "nuts_compare: out of device memory (sums)"; return NUTS_E_HIP; }
+    h->out_cap = out;
+  }
+  return NUTS_OK;
+}
+
+// adds the slots part[nwg][na] and copies the na sums to the host
+static int cmp_collect(nuts_compare* h, int nwg, int64_t na, double* host) {
+  hipLaunchKernelGGL(k_cmp_reduce, dim3((unsigned)na), dim3(CMP_BLOCK), 0, 0, (const double*)h->part, (int64_t)nwg, na, h->out);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpy(host, h->out, (size_t)na * sizeof(double), hipMemcpyDeviceToHost));
+  return NUTS_OK;
+}
+
+static int cmp_ready(nuts_compare* h, const char* what) {
+  if (!h) { g_err = std::string(what) + ": null handle"; return NUTS_E_ARG; }
+  for (int k = 0; k < h->K; ++k)
+    if (!h->set[k]) { g_err = std::string(what) + ": row " + std::to_string(k) + " of " + std::to_string(h->K) + " is not set"; return NUTS_E_ARG; }
+  return NUTS_OK;
+}
+
+extern "C" void nuts_compare_destroy(nuts_compare* h) {
+  if (!h) return;
+  hipDeviceSynchronize();
+  for (double* ptr : {h->e, h->p, h->stage, h->part, h->out}) if (ptr) hipFree(ptr);
+  delete h;
+}
+
+extern "C" nuts_compare* nuts_compare_create(int64_t N, int32_t K) {
+  if (N < 1 || K < 2 || K > CMP_MAXK) {
+    g_err = "nuts_compare_create: N >= 1 and 2 <= K <= " + std::to_string(CMP_MAXK) + " models, not N = " + std::to_string(N) + ", K = " + std::to_string(K);
+    return nullptr;
+  }
+  if (nuts_device_count() < 1) { g_err = "no HIP device visible: nuts_compare requires an MI355X (gfx950); there is no CPU fallback"; return nullptr; }
+  nuts_compare* h = new nuts_compare();
+  h->N = N; h->K = K;
+  h->e = dev_alloc<double>((size_t)K * (size_t)N);
+  h->p = dev_alloc<double>((size_t)K * (size_t)N);
+  h->stage = dev_alloc<double>((size_t)N);
+  if (!h->e || !h->p || !h->stage) {
+    nuts_compare_destroy(h);
+    g_err = "nuts_compare_create: out of device memory (16 K N + 8 N bytes)";
+    return nullptr;
+  }
+  return h;
+}
+
+extern "C" int nuts_compare_set(nuts_compare* h, int32_t k, const double* elpd_i, const int64_t* order) {
+  if (!h || !elpd_i) { g_err = "nuts_compare_set: null argument"; return NUTS_E_ARG; }
+  if (k < 0 || k >= h->K) { g_err = "nuts_compare_set: model " + std::to_string(k) + " outside 0 .. " + std::to_string(h->K - 1); return NUTS_E_ARG; }
+  const int64_t N = h->N;
+  if (order) {
+    std::vector<bool> seen((size_t)N, false);
+    for (int64_t j = 0; j < N; ++j) {
+      if (order[j] < 0 || order[j] >= N || seen[(size_t)order[j]]) {
+        g_err = "nuts_compare_set: order is not a permutation of 0 .. " + std::to_string(N - 1) + " (entry " + std::to_string(j) + " = " + std::to_string(order[j]) + ")";
+        return NUTS_E_ARG;
+      }
+      seen[(size_t)order[j]] = true;
+    }
+  }
+  int64_t bad = -1, bad_j = -1;
+  for (int64_t j = 0; j < N; ++j)
+    if (!std::isfinite(elpd_i[j])) {
+      const int64_t i = order ? order[j] : j;
+      if (bad < 0 || i < bad) { bad = i; bad_j = j; }
+    }
+  if (bad >= 0) {
+    char val[32];
+    std::snprintf(val, sizeof val, "%g", elpd_i[bad_j]);
+    g_err = "nuts_compare_set: model " + std::to_string(k) + " has the non-finite value " + val + " at observation " + std::to_string(bad) +
+            " (PSIS gives -inf or NaN where a draw's density is 0): such a model is not compared";
+    return NUTS_E_ARG;
+  }
+  int64_t* order_dev = nullptr;
+  if (order) {
+    order_dev = dev_upload<int64_t>(order, (size_t)N);
+    if (!order_dev) { g_err = "nuts_compare_set: out of device memory (order)"; return NUTS_E_HIP; }
+  }
+  hipError_t e = hipMemcpy(h->stage, elpd_i, (size_t)N * sizeof(double), hipMemcpyHostToDevice);
+  if (e == hipSuccess) {
+    hipLaunchKernelGGL(k_cmp_scatter, dim3((unsigned)((N + CMP_BLOCK - 1) / CMP_BLOCK)), dim3(CMP_BLOCK), 0, 0, (const double*)h->stage,
+                       (const int64_t*)order_dev, N, h->e + (size_t)k * (size_t)N);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipStreamSynchronize(0);
+  if (order_dev) hipFree(order_dev);
+  HIPCHK_RET(e, "nuts_compare_set", NUTS_E_HIP);
+  h->set[k] = true;
+  h->terms = false;
+  return NUTS_OK;
+}
+
+extern "C" int nuts_compare_moments(nuts_compare* h, double* elpd, double* se, double* dse, int32_t* best) {
+  int rc = cmp_ready(h, "nuts_compare_moments");
+  if (rc != NUTS_OK) return rc;
+  const int64_t N = h->N;
+  const int K = h->K;
+  int nwg;
+  if ((rc = cmp_wgs((N + CMP_BLOCK - 1) / CMP_BLOCK, 1024, 65535, &nwg)) != NUTS_OK) return rc;
+  if ((rc = cmp_reserve(h, (size_t)nwg * 2 * K, 2 * K)) != NUTS_OK) return rc;
+  double s[2 * CMP_MAXK];
+  CmpVec mean = {}, dmean = {};
+  CMP_DISPATCH(K, hipLaunchKernelGGL((k_cmp_moments<KK, 0>), dim3(nwg), dim3(CMP_BLOCK), 0, 0, (const double*)h->e, N, mean, dmean, 0, h->part));
+  if ((rc = cmp_collect(h, nwg, K, s)) != NUTS_OK) return rc;
+  int b = 0;
+  for (int k = 1; k < K; ++k) if (s[k] > s[b]) b = k;
+  double sum[CMP_MAXK];
+  for (int k = 0; k < K; ++k) { sum[k] = s[k]; mean.v[k] = s[k] / (double)N; dmean.v[k] = (s[b] - s[k]) / (double)N; }
+  CMP_DISPATCH(K, hipLaunchKernelGGL((k_cmp_moments<KK, 1>), dim3(nwg), dim3(CMP_BLOCK), 0, 0, (const double*)h->e, N, mean, dmean, b, h->part));
+  if ((rc = cmp_collect(h, nwg, 2 * K, s)) != NUTS_OK) return rc;
+  for (int k = 0; k < K; ++k) {
+    if (elpd) elpd[k] = sum[k];
+    if (se) se[k] = std::sqrt((double)N * (s[k] / (double)N));
+    if (dse) dse[k] = std::sqrt((double)N * (s[K + k] / (double)N));
+  }
+  if (best) *best = b;
+  return NUTS_OK;
+}
+
+struct CmpPassCtx { nuts_compare* h; int nwg; int rc; };
+static bool cmp_device_pass(void* ctx, const double* w, double* sums) {
+  CmpPassCtx* c = static_cast<CmpPassCtx*>(ctx);
+  nuts_compare* h = c->h;
+  const int K = h->K;
+  CmpVec wv = {};
+  for (int k = 0; k < K; ++k) wv.v[k] = w[k];
+  CMP_DISPATCH(K, hipLaunchKernelGGL((k_cmp_stack_pass<KK>), dim3(c->nwg), dim3(CMP_BLOCK), 0, 0, (const double*)h->p, h->N, wv, h->part));
+  c->rc = cmp_collect(h, c->nwg, CMP_NACC(K), sums);
+  return c->rc == NUTS_OK;
+}
+
+extern "C" int nuts_compare_stacking(nuts_compare* h, double* w, double* objective, double* kkt_gap, int32_t* passes) {
+  int rc = cmp_ready(h, "nuts_compare_stacking");
+  if (rc != NUTS_OK) return rc;
+  if (!w) { g_err = "nuts_compare_stacking: null argument"; return NUTS_E_ARG; }
+  const int64_t N = h->N;
+  const int K = h->K;
+  int nwg;
+  if ((rc = cmp_wgs((N + CMP_BLOCK - 1) / CMP_BLOCK, 1024, 65535, &nwg)) != NUTS_OK) return rc;
+  if ((rc = cmp_reserve(h, (size_t)nwg * CMP_NACC(CMP_MAXK), CMP_NACC(CMP_MAXK))) != NUTS_OK) return rc;
+  if (!h->terms) {
+    CMP_DISPATCH(K, hipLaunchKernelGGL((k_cmp_terms<KK>), dim3(nwg), dim3(CMP_BLOCK), 0, 0, (const double*)h->e, N, h->p, h->part));
+    if ((rc = cmp_collect(h, nwg, 1, &h->sum_m)) != NUTS_OK) return rc;
+    h->terms = true;
+  }
+  CmpPassCtx ctx{h, nwg, NUTS_OK};
+  double ld = 0.0, gap = 0.0;
+  int np = 0;
+  if (!cmp_solve(K, N, cmp_device_pass, &ctx, 1e-10, 64, w, &ld, &gap, &np)) return ctx.rc;
+  if (objective) *objective = h->sum_m + ld;
+  if (kkt_gap) *kkt_gap = gap;
+  if (passes) *passes = np;
+  return NUTS_OK;
+}
+
+extern "C" int nuts_compare_bb(nuts_compare* h, int64_t b_samples, uint64_t seed, double* w, double* se_bb, double* z) {
+  int rc = cmp_ready(h, "nuts_compare_bb");
+  if (rc != NUTS_OK) return rc;
+  if (b_samples < 1 || b_samples > 65536) { g_err = "nuts_compare_bb: b_samples must lie in 1 .. 65536, not " + std::to_string(b_samples); return NUTS_E_ARG; }
+  const int64_t N = h->N, nslab = (N + CMP_BB_SLAB - 1) / CMP_BB_SLAB;
+  const int K = h->K, K1 = K + 1;
+  int nwg;
+  if ((rc = cmp_wgs(nslab, 4096, 4096, &nwg)) != NUTS_OK) return rc;
+  const int64_t chunk = std::min<int64_t>(CMP_BB_CHUNK, (b_samples + 1) & ~(int64_t)1);
+  if ((rc = cmp_reserve(h, (size_t)nwg * (size_t)chunk * K1, (size_t)chunk * K1)) != NUTS_OK) return rc;
+  std::vector<double> zz((size_t)b_samples * K), sums((size_t)chunk * K1);
+  const PPKey key = pp_key(seed);
+  for (int64_t b0 = 0; b0 < b_samples; b0 += chunk) {
+    const int64_t nb = std::min(chunk, b_samples - b0);
+    const int npairs = (int)((nb + 1) / 2);
+    CMP_DISPATCH(K, hipLaunchKernelGGL((k_cmp_bb<KK>), dim3(nwg), dim3(WAVE), 0, 0, (const double*)h->e, N, nslab, key, (uint32_t)(b0 / 2), npairs, h->part));
+    if ((rc = cmp_collect(h, nwg, (int64_t)2 * npairs * K1, sums.data())) != NUTS_OK) return rc;
+    for (int64_t b = 0; b < nb; ++b)
+      for (int k = 0; k < K; ++k) zz[(size_t)(b0 + b) * K + k] = (double)N * sums[(size_t)b * K1 + 1 + k] / sums[(size_t)b * K1];
+  }
+  // per replicate the softmax over the models; the mean over the replicates and the population standard deviation of z_.k (two passes)
+  double wsum[CMP_MAXK] = {}, zmean[CMP_MAXK] = {}, zss[CMP_MAXK] = {};
+  for (int64_t b = 0; b < b_samples; ++b) {
+    const double* row = zz.data() + (size_t)b * K;
+    double m = row[0], tot = 0.0, u[CMP_MAXK];
+    for (int k = 1; k < K; ++k) m = std::max(m, row[k]);
+    for (int k = 0; k < K; ++k) { u[k] = std::exp(row[k] - m); tot += u[k]; }
+    for (int k = 0; k < K; ++k) { wsum[k] += u[k] / tot; zmean[k] += row[k]; }
+  }
+  for (int k = 0; k < K; ++k) zmean[k] /= (double)b_samples;
+  for (int64_t b = 0; b < b_samples; ++b)
+    for (int k = 0; k < K; ++k) { const double d = zz[(size_t)b * K + k] - zmean[k]; zss[k] += d * d; }
+  for (int k = 0; k < K; ++k) {
+    if (w) w[k] = wsum[k] / (double)b_samples;
+    if (se_bb) se_bb[k] = std::sqrt(zss[k] / (double)b_samples);
+  }
+  if (z) std::memcpy(z, zz.data(), zz.size() * sizeof(double));
   return NUTS_OK;
 }
 
