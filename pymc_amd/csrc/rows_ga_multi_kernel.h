@@ -85,13 +85,64 @@ __device__ __forceinline__ void gam_load_packed(const uint32_t* base /* first dw
   t.last = base[6 * 4 * WAVE + lane];
 }
 
+// The same two requests for the paired launch's loop (SH), from a SCALAR tile address (`gam_uniform`: the compiler then adds the
+// lane's byte offset where the loads are issued, instead of keeping `base + lane` of the whole array as a per-lane 64-bit address
+// across the loop and multiplying the tile index into it per lane).  The global address space is spelled out: an address that
+// was an integer is otherwise a flat one.
+typedef const __attribute__((address_space(1))) char gam_gc;
+__device__ __forceinline__ uint64_t gam_uniform(uint64_t a) {
+  return ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(a >> 32)) << 32) | (uint32_t)__builtin_amdgcn_readfirstlane((int)(a & 0xffffffffull));
+}
+template <int DX>
+__device__ __forceinline__ void gam_load_s(uint64_t tile, uint64_t ytile, uint32_t lane, typename GaTileSel<DX>::type& t) {
+  tile = gam_uniform(tile); ytile = gam_uniform(ytile);
+  gam_gc* b = (gam_gc*)tile + lane * 16u;
+#pragma unroll
+  for (int k = 0; k < DX; ++k) t.c[k] = *(const __attribute__((address_space(1))) ga_v2d*)(b + k * (16 * WAVE));
+  t.y = *(const __attribute__((address_space(1))) uint16_t*)((gam_gc*)ytile + lane * 2u);
+}
+__device__ __forceinline__ void gam_load_packed_s(uint64_t tile, uint32_t lane, GaTileRegsP& t) {
+  tile = gam_uniform(tile);
+  gam_gc* b = (gam_gc*)tile + lane * 16u;
+#pragma unroll
+  for (int k = 0; k < 6; ++k) t.p[k] = *(const __attribute__((address_space(1))) ga_v4u*)(b + k * (16 * WAVE));
+  t.last = *(const __attribute__((address_space(1))) uint32_t*)((gam_gc*)tile + 6 * 16 * WAVE + lane * 4u);
+}
+
+// Row k of a lane under BOTH coefficient vectors of a paired launch (SH), the two chains side by side: a wave that evaluates one
+// row under one vector has ONE dependent fp64 chain in flight (logit_row: ~40 operations, each waiting for the one before), and
+// sixteen such waves per CU leave the pipe idle most of the time (tools/fp64_rate_lab.hip).  The same row under the two vectors
+// is two independent chains that share their x operands -- logit_row2 issues them statement by statement next to each other --
+// and needs one row's x only: the other row of the lane waits in `xx`, no second set of x registers is live.
+// Per (chain, row) the operations and their order are ga_tile's (eta summed over d = 0 .. 7 from 0.0, logit_row2 bitwise
+// logit_row, the mask, acc[d] = fma(r, x[d], acc[d])); neither chain reads a value of the other.
+template <int K>
+__device__ __forceinline__ void gam_row_pair(const double (&x)[8][2], uint32_t yb, const double (&beta)[2][8], int nvalid, int lane,
+                                             double (&acc)[2][8], double (&lp)[2]) {
+  double eta[2] = {0.0, 0.0}, yk[2], l[2], rr[2];
+#pragma unroll
+  for (int d = 0; d < 8; ++d) { eta[0] = fma(x[d][K], beta[0][d], eta[0]); eta[1] = fma(x[d][K], beta[1][d], eta[1]); }
+  yk[0] = yk[1] = (double)((yb >> (8 * K)) & 0xffu);
+  logit_row2(eta, yk, l, rr);
+  // lane * 2 + K < nvalid (only the zero-padded last tile of a group has rows to mask), on the lane's byte offset into a 16 B-per-lane
+  // plane, which the request holds in a register anyway, against a scalar
+  const bool in = (uint32_t)lane * 16u < (uint32_t)((nvalid - K + 1) >> 1) * 16u;
+#pragma unroll
+  for (int c = 0; c < 2; ++c) {
+    lp[c] += in ? l[c] : 0.0;
+    rr[c] = in ? rr[c] : 0.0;
+  }
+#pragma unroll
+  for (int d = 0; d < 8; ++d) { acc[0][d] = fma(rr[0], x[d][K], acc[0][d]); acc[1][d] = fma(rr[1], x[d][K], acc[1][d]); }
+}
+
 // D = 8 covariates, two rows per lane, two tile buffers per wave; DX stored columns (7: the intercept column is not stored).  Grid: GAM_MAXC control workgroups + G group workgroups; block: the W waves of the
 // model's layout (a wave's chunk of tiles is fixed when the model is created).
 // Edge pairing (SH) runs at FOUR waves per SIMD: GAM_MAXC + G workgroups of W waves are then resident at once, as the plain
 // launch's are (rows_ga_kernel.h: "G workgroups of W waves must all be resident"; at three waves per SIMD 1024 of the benchmark's
 // 1256 workgroups were, and the rest ran as a second round on a nearly empty chip).  128 registers hold ONE tile buffer and the
-// rows of a lane one after the other: a tile is decoded into `xx`, the wave's next tile is requested into the same registers, and
-// both coefficient vectors are evaluated on `xx` while it arrives.  PK (SH only): the tiles are the packed ones the chain's own
+// rows of a lane one after the other, each under both coefficient vectors at once (gam_row_pair): a tile is decoded into `xx`,
+// row 0 is evaluated, the wave's next tile is requested into the same registers, and row 1 is evaluated while it arrives.  PK (SH only): the tiles are the packed ones the chain's own
 // launch streams (R.Xp, 6400 B per tile instead of 7296), decoded and patched exactly as k_rows_ga does.
 template <int NC, int OCC, int DX, bool SH = false, int PK = 0>
 __global__ __launch_bounds__(64 * GA_MAXW, OCC) void k_rows_ga_multi(ModelDev md, GaMultiArgs<NC, SH> ma) {
@@ -265,23 +316,65 @@ __global__ __launch_bounds__(64 * GA_MAXW, OCC) void k_rows_ga_multi(ModelDev md
       _Pragma("unroll") for (int c = 0; c < NC; ++c) ga_tile<8, 2, (NC == 2)>(xx, yy, beta[c], nv, lane, acc[c], lp[c]); \
     }
     if constexpr (ONE) {
-      // one buffer, four waves per SIMD: decode (packed: and patch) the tile into `xx`, re-request the buffer, then the arithmetic
+      // one buffer, four waves per SIMD: decode (packed: and patch) the tile into `xx`; row 0, re-request the buffer, row 1
       uint32_t ebase20 = 0;
       if constexpr (PK) ebase20 = R.ga_pack_ebase20;
-      for (int i = 0; i < n; ++i) {
-        if (i == nsw) flush();
+      // `local_at` as one scalar select (a branch here splits the arithmetic into blocks the request cannot be pinned between)
+      const int radd = rev ? nA : 0, rsub = rev ? nsw : 0;
+      // (the stream's pointers as scalars of their own: read out of the model's kernel argument inside the loop, each drags the
+      // sixteen-register block it was loaded with back from its spill slot, once per tile)
+      uint64_t xbase = (uint64_t)(PK ? (const void*)R.Xp : (const void*)R.Xt), ybase = (uint64_t)R.y;
+      const uint64_t* pexc_idx = R.ga_pexc_idx;
+      const RpExc* pexc = R.ga_pexc;
+      asm("" : "+s"(xbase), "+s"(ybase), "+s"(pexc_idx), "+s"(pexc));
+      auto local1 = [&](int i) { return i + (i < nsw ? radd : -rsub); };
+      auto issue1 = [&](int i) {   // (unconditional: past the end it re-reads the wave's last tile)
+        const int loc = local1(min(i, nm1));
+        const int64_t off = cbase + (int64_t)loc * TS;
+        if constexpr (PK) {
+          gam_load_packed_s(xbase + (uint64_t)off * 4, (uint32_t)lane, ta);
+          ea = ga_exc_range(pexc_idx, te0 + loc);
+        } else {
+          gam_load_s<DX>(xbase + (uint64_t)off * 8, ybase + (uint64_t)(off / DX), (uint32_t)lane, ta);
+        }
+      };
+      auto stage = [&](int i) {
         double xx[8][2];
         if constexpr (PK) {
           ga_unpack(ta, ebase20, xx);
-          if ((uint32_t)(ea >> 32) != 0) ga_patch(R.ga_pexc, ea, lane, xx);
+          if ((uint32_t)(ea >> 32) != 0) ga_patch(pexc, ea, lane, xx);
         } else {
           ga_unpack(ta, xx);
         }
         const uint32_t yy = ga_ybits(ta);
-        const int nv = local_at(i) == l_last ? n_last : SPAN;
-        issue(i + 1, ta);
-#pragma unroll
-        for (int c = 0; c < NC; ++c) ga_tile<8, 2>(xx, yy, beta[c], nv, lane, acc[c], lp[c]);
+        const int nv = local1(i) == l_last ? n_last : SPAN;
+        // row 0 under both vectors, then the request (row 0's x registers are dead: they make room for the tile), then row 1 while
+        // it arrives.  The barriers keep the request where it is written: above row 0 it would not fit 128 registers.  With eight
+        // stored columns it does not fit between the rows either (33 tile registers + 16 of row 1: one reload per tile): that
+        // instantiation requests behind row 1, the other waves of the SIMD cover its wait.
+        constexpr bool MID = DX == 7;
+        gam_row_pair<0>(xx, yy, beta, nv, lane, acc, lp);
+        __builtin_amdgcn_sched_barrier(0);
+        if constexpr (MID) { issue1(i + 1); __builtin_amdgcn_sched_barrier(0); }
+        gam_row_pair<1>(xx, yy, beta, nv, lane, acc, lp);
+        if constexpr (!MID) { __builtin_amdgcn_sched_barrier(0); issue1(i + 1); }
+      };
+      if constexpr (PK) {
+        // the wave's two halves as two loops, the mid-stream flush between them: as `if (i == nsw) flush()` inside ONE loop its
+        // masks and addresses stay live across the arithmetic of every tile, and most of `beta` is then reloaded from its spill
+        // lanes once per tile (61 `v_readlane` per tile against 14).  The raw kernels keep one loop: split, the seven-column one
+        // reloads four values from scratch per tile of its second half.
+        const int n0 = min(nsw, n);
+        for (int i = 0; i < n0; ++i) stage(i);
+        if (nsw < n) {
+          flush();
+          for (int i = nsw; i < n; ++i) stage(i);
+        }
+      } else {
+        for (int i = 0; i < n; ++i) {
+          if (i == nsw) flush();
+          stage(i);
+        }
       }
     } else if constexpr (TWO) {
       for (int i = 0; i < n; i += 2) {
