@@ -556,6 +556,9 @@ static void launch_vector(nuts_model* m, const ArenaDev& A, const EvalIO& io, in
   if (md.n_lins > 0) {
     for (int l = 0; l < md.n_lins; ++l) {
       const LinDev& L = m->lins_host[l];
+      bool read = false;   // a predictor only Deterministics read (evaluated on the host) has no adjoints and no target: no backward pass
+      for (int k = 0; k < L.K; ++k) read = read || L.col[k].n_use > 0;
+      if (!read) continue;
       if (L.N == 1) { hipLaunchKernelGGL(k_lin_bwd1, dim3(L.K), dim3(1024), 0, m->stream, md, A, io, l); continue; }
       const dim3 grid((unsigned)L.nchunk, (unsigned)L.P);
 #define LIN_BWD(KT) hipLaunchKernelGGL(k_lin_bwd<KT>, grid, dim3(256), 0, m->stream, md, A, io, l)

@@ -85,6 +85,7 @@ __global__ __launch_bounds__(1024) void k_lin_fwd1(ModelDev md, ArenaDev A, Eval
 
 // d logp / d eta_k[i]: what the sweeps of the factors that read the column left behind
 __device__ __forceinline__ double lin_adj(const ModelDev& md, const LinCol& c, int64_t i) {
+  if (c.n_use == 0) return 0.0;   // a column no factor reads (a Deterministic's): adj_off[0] is not its own, md.adj may be null
   double a = md.adj[c.adj_off[0] + i];
   for (int u = 1; u < c.n_use; ++u) a += md.adj[c.adj_off[u] + i];
   return a;

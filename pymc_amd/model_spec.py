@@ -256,7 +256,7 @@ class GlmRows:
     beta_derived: Optional[int] = None   # index (into ModelSpec.factors) of the D_DERIVED factor that is beta
 
 
-LIN_MAXK, MAX_LINS, LIN_MAXP = 16, 4, 512
+LIN_MAXK, MAX_LINS, LIN_MAXP, LIN_MAXUSE = 16, 4, 512, 4
 
 
 @dataclass
@@ -526,7 +526,8 @@ def engine_refusal(spec: "ModelSpec") -> Optional[str]:
         deferred += sum(spec.vars[k].size for k in (rows.mu, rows.sigma) if spec.vars[k].size != 1)
     bterm_vars: List[int] = []
     n_derived = 0
-    for f in spec.factors:
+    lin_readers: Dict[Tuple[int, int], set] = {}      # (predictor, column) -> the factors that read it (csrc/engine.hip `lin_uses`)
+    for fi, f in enumerate(spec.factors):
         prog = tuple(getattr(f, "prog", ()) or ())
         if not 1 <= len(f.args) <= 4 or f.size < 1:
             return "factor with a bad argument count or size"
@@ -570,6 +571,7 @@ def engine_refusal(spec: "ModelSpec") -> Optional[str]:
                     return "linear predictor: one row per element of the factor (or a single row that broadcasts)"
                 if f.dist == D_DERIVED:
                     return "a derived vector cannot read a linear predictor"
+                lin_readers.setdefault((o.ref, int(o.c)), set()).add(fi)
             elif o.kind == OP_DATA:
                 if not 0 <= o.ref < nd:
                     return "factor refers to a missing data vector"
@@ -615,6 +617,8 @@ def engine_refusal(spec: "ModelSpec") -> Optional[str]:
                 return "linear predictor: coefficients must be a variable or a NUTS_D_DERIVED factor"
             if off < 0 or stride < 0 or (stride == 0 and P > 1) or off + (P - 1) * stride >= size:
                 return "linear predictor: coefficients beyond the end of their variable"
+    if any(len(r) > LIN_MAXUSE for r in lin_readers.values()):      # (`build_lins`: LinCol has LIN_MAXUSE adjoint offsets)
+        return "a linear predictor column is read by too many factors (LIN_MAXUSE)"
     return None
 
 
