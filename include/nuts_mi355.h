@@ -403,6 +403,26 @@ int nuts_ppc_update(nuts_ppc *p, const double *q, int64_t S);
 int nuts_ppc_read(nuts_ppc *p, double *mean_i, double *var_i, double *n_lt_i, double *n_eq_i, int64_t *n_draws);
 int nuts_ppc_read_stats(nuts_ppc *p, double *T /* [n_draws][4] */, double *T_obs /* [4] */);
 void nuts_ppc_destroy(nuts_ppc *p);
+/* Prior draws (`pm.sample_prior_predictive`, its first half): S positions drawn from the PRIORS of the free variables, in ancestral
+ * order, on the device (pymc_amd/csrc/prior.h, prior_kernel.h).  A free variable has a samplable prior when exactly one factor has
+ * the bare variable as its argument 0, the variable's size, and a continuous family nuts_model_predictive draws from; the factor's
+ * other arguments and its program may read constants, data, other variables and temporaries.  The variables are drawn level by level
+ * (a variable's level is one more than the largest level of the variables its prior reads), one launch per level; the value of
+ * (variable, draw s, element i) is a function of (seed, the variable's place in the spec, s, i) and of the parents' values at draw
+ * s -- not of the batch size (64 draws; option NUTS_PRIOR_B: fewer) or of how S is split over calls.  s is the GLOBAL draw number
+ * draw0 + the position in the call.  The counter has bit 63 of the element index set, which no observation index has: under one
+ * seed a prior stream never coincides with a stream of nuts_model_predictive.  Under `w ~ Dirichlet(alpha)` the mixture node's
+ * weights are drawn by the node's own rule (prior.h).  Each draw is pushed through the FORWARD transform of its variable: q_out holds
+ * unconstrained positions, what nuts_model_predictive and nuts_ppc_update take.  A constrained draw on the boundary of its support
+ * maps to an infinite position, invalid parameters give NaN for the element and, through the arithmetic, for whatever reads it;
+ * neither is clamped or hidden: *n_nonfinite is the count of non-finite entries of q_out.
+ * Refused (NUTS_E_ARG, text in nuts_last_error() naming the variable by its place in the spec): a variable with no such factor or
+ * with more than one; a prior of family TRUNCNORMAL, BINOMIAL, POTENTIAL, DERIVED or of a discrete one; any NUTS_D_POTENTIAL factor
+ * that reads a variable or a linear predictor (it reweights the prior); a prior that reads a NUTS_OP_LIN operand; a model with an
+ * MvNormal node or a conditional mixture; a variable index above 16383; priors that read each other in a cycle; a member of a chain
+ * group; a draw number of 2^32 or more. */
+int nuts_model_prior(nuts_model *m, int64_t S, uint64_t seed, int64_t draw0,
+                     double *q_out /* host [S][ndim], UNCONSTRAINED */, int64_t *n_nonfinite /* may be NULL */);
 /* LOO predictive checks (`az.loo_pit`, the LOO predictive mean and variance of each observation): a SECOND pass over the draws of
  * a finished nuts_psis.  Once all n_draws are in, the PSIS state fixes the normalised Pareto-smoothed weight w[s][i] of every draw:
  * a draw outside the tail keeps its raw weight, a draw of the tail takes the generalised-Pareto quantile of its rank in the sorted

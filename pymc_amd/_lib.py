@@ -296,6 +296,7 @@ SYMBOLS = {
     "nuts_psis_read_raw": (C.c_int, [_VP, _PD, _PD, C.POINTER(C.c_int64)]),
     "nuts_psis_destroy": (None, [_VP]),
     "nuts_model_predictive": (C.c_int, [_VP, C.c_int32, C.c_int32, _PD, C.c_int64, C.c_uint64, C.c_int64, _PD]),
+    "nuts_model_prior": (C.c_int, [_VP, C.c_int64, C.c_uint64, C.c_int64, _PD, C.POINTER(C.c_int64)]),
     "nuts_ppc_create": (_VP, [_VP, C.c_int32, C.c_int32, C.c_uint64]),
     "nuts_ppc_update": (C.c_int, [_VP, _PD, C.c_int64]),
     "nuts_ppc_read": (C.c_int, [_VP, _PD, _PD, _PD, _PD, C.POINTER(C.c_int64)]),

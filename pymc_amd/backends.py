@@ -25,7 +25,7 @@ from typing import Dict, List, Optional, Sequence
 import numpy as np
 
 from pymc_amd.model_spec import ModelSpec
-from pymc_amd.trace import backward
+from pymc_amd.trace import backward, deterministic_shape
 
 
 class BackendError(Exception):   # base.py:43-44
@@ -61,7 +61,7 @@ class NDArray:
         self._dets = [(nm, d) for nm, d in getattr(model, "deterministics", {}).items() if vars is None or nm in vars]
         for nm, (_, _, size) in self._dets:
             self.varnames.append(nm)
-            self.var_shapes[nm] = getattr(model, "deterministic_shapes", {}).get(nm, () if size == 1 else (size,))
+            self.var_shapes[nm] = deterministic_shape(model, nm)
         self.var_dtypes = {nm: np.dtype("float64") for nm in self.varnames}
         self.chain = None
         self.sampler_vars = None
@@ -131,18 +131,10 @@ class NDArray:
         self.draw_idx += 1
 
     def _record_deterministics(self, positions: np.ndarray, i: int) -> None:
-        from pymc_amd.model_spec import eval_program
+        from pymc_amd.trace import deterministics
 
-        x = np.empty_like(positions)                    # constrained values, spec layout
-        for v in self.model.vars:
-            blk = positions[:, v.offset : v.offset + v.size]
-            # (a simplex-transformed variable has K constrained elements for its K - 1 stored ones: no slot in this layout.  No
-            # Deterministic can refer to it -- the lowering leaves such a one out of the trace with a warning, `ModelBuilder` has no
-            # operand for it -- so its block keeps the stored values)
-            x[:, v.offset : v.offset + v.size] = blk if getattr(v, "simplex", False) else backward(v, blk)
-        for nm, (prog, term, size) in self._dets:
-            val = eval_program(self.model, prog, term, x)
-            self.samples[nm][i : i + len(positions)] = np.broadcast_to(val, (len(positions), size)).reshape((len(positions), *self.var_shapes[nm]))
+        for nm, val in deterministics(self.model, positions, [nm for nm, _ in self._dets]).items():
+            self.samples[nm][i : i + len(positions)] = val
 
     def record_batch(self, positions: np.ndarray, stats_list: Sequence[Sequence[dict]], *, in_warmup: bool = False) -> None:
         """K raveled positions `(K, n)` in `model.value_vars` order (a multi-draw call of the device step) and their K stats

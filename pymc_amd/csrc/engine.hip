@@ -26,6 +26,7 @@
 #include "mixture_kernel.h"
 #include "loglik_kernel.h"
 #include "predictive_kernel.h"
+#include "prior_kernel.h"
 #include "loo_pit_kernel.h"
 #include "summary_kernel.h"
 #include "compare_kernel.h"
@@ -214,6 +215,13 @@ struct nuts_model {
   int32_t* ll_dead = nullptr;
   int64_t ll_stage_n = 0, ll_par_n = 0;
   int n_waic = 0;                  // live nuts_waic / nuts_psis / nuts_ppc handles on this model
+  // prior draws (prior_kernel.h): the ancestral order as levels of variables, or why the model has none (prior_build_plan, when the
+  // model is created); the levels' tables on the device one after the other and ONE batch of positions [PRIOR_B][n], allocated when
+  // first asked for
+  std::string prior_err;
+  std::vector<std::vector<PriorVar>> prior_levels;
+  PriorVar* prior_tab = nullptr;
+  double* prior_q = nullptr;
 
   template <typename T>
   T* keep(T* p) {
@@ -2017,6 +2025,8 @@ static bool build_glm(nuts_model* m, const nuts_model_spec* s, const CompiledSpe
   return true;
 }
 
+static void prior_build_plan(nuts_model* m, const nuts_model_spec* s);
+
 // Every step sets g_err and returns false on refusal; nuts_model_create destroys the half-built model in ONE place.
 static bool model_build(nuts_model* m, const nuts_model_spec* s) {
   ModelDev& md = m->md;
@@ -2031,6 +2041,7 @@ static bool model_build(nuts_model* m, const nuts_model_spec* s) {
   CompiledSpec cs;
   if (!compile_spec(m, s, cs)) return false;
   m->fac_host = cs.fac;
+  prior_build_plan(m, s);
   {   // the spec's data pool, then the engine's own vectors (derived values / seeds), zeroed
     double* pool = m->keep(dev_alloc<double>((size_t)std::max<int64_t>(s->data_pool_len + m->pool_extra, 1)));
     if (pool) {
@@ -2144,7 +2155,8 @@ extern "C" void nuts_model_destroy(nuts_model* m) {
   if (m->set_pin) hipHostFree(m->set_pin);
   if (m->group) group_remove_model(m->group, m);
   for (void* p : m->owned) if (p) hipFree(p);
-  for (void* p : {(void*)m->ll_q, (void*)m->ll_stage, (void*)m->ll_par, (void*)m->ll_sc, (void*)m->ll_dead, (void*)m->ll_lfact}) if (p) hipFree(p);
+  for (void* p : {(void*)m->ll_q, (void*)m->ll_stage, (void*)m->ll_par, (void*)m->ll_sc, (void*)m->ll_dead, (void*)m->ll_lfact, (void*)m->prior_tab,
+                  (void*)m->prior_q}) if (p) hipFree(p);
   for (auto e : m->ev) hipEventDestroy(e);
   if (m->host_pin) hipHostFree(m->host_pin);
   if (m->own_stream) hipStreamDestroy(m->own_stream);
@@ -2721,6 +2733,153 @@ extern "C" int nuts_model_predictive(nuts_model* m, int32_t kind, int32_t index,
     HIPCHK(hipStreamSynchronize(m->stream));
   }
   HIPCHK(hipGetLastError());
+  return NUTS_OK;
+}
+
+// ---- prior draws (prior.h, prior_kernel.h) -------------------------------------------------------------------------------------------
+// The plan: which factor is a variable's prior, and the ancestral order as levels (level(v) = 1 + the largest level of the variables
+// its prior reads; 0 when it reads none).  Host only, when the model is created; a model without a samplable prior keeps the reason
+// (m->prior_err) and nuts_model_prior returns it.  pymc_amd/predictive.py `prior_refusal` restates the rules, in this order.
+#define PRIOR_B 64   // draws per batch of nuts_model_prior: the device holds [PRIOR_B][n] positions (option NUTS_PRIOR_B: fewer)
+
+static const char* prior_family_name(int dist) {
+  static const char* names[] = {"Normal", "HalfNormal", "Cauchy", "HalfCauchy", "StudentT", "Beta", "Exponential", "Uniform", "BernoulliLogit",
+                                "LogNormal", "Bernoulli", "TruncatedNormal", "Potential", "Binomial", "Gamma", "InverseGamma", "Laplace", "Poisson", "Derived"};
+  return dist >= 0 && dist <= NUTS_D_DERIVED ? names[dist] : "unknown";
+}
+
+static void prior_build_plan(nuts_model* m, const nuts_model_spec* s) {
+  const int nv = s->n_vars, nf = s->n_factors;
+  m->prior_levels.clear();
+  m->prior_err.clear();
+  auto refuse_prior = [&](const std::string& why) { m->prior_levels.clear(); m->prior_err = why; };
+  // every operand of a factor: its arguments (from argument `first_arg` on), then its program
+  auto each_operand = [&](const nuts_factor& f, int first_arg, auto&& fn) {
+    for (int a = first_arg; a < f.nargs && a < 4; ++a)
+      for (const nuts_operand* o : {&f.arg[a].a, &f.arg[a].b, &f.arg[a].c}) fn(*o);
+    for (int i = 0; i < f.n_instr && s->instrs; ++i) {
+      const nuts_instr& I = s->instrs[f.instr_off + i];
+      for (const nuts_operand* o : {&I.x, &I.y, &I.z}) fn(*o);
+    }
+  };
+  if (s->mvn_k > 0)
+    return refuse_prior("variable " + std::to_string(s->mvn_var) + " is the MvNormal node's: its prior draw needs a Cholesky factor on the device");
+  if (s->mix_N > 0 && s->mix_assign >= 0) return refuse_prior("the mixture node is a conditional mixture: its assignments are another step method's");
+  for (int fi = 0; fi < nf; ++fi) {
+    const nuts_factor& f = s->factors[fi];
+    if (f.dist != NUTS_D_POTENTIAL) continue;
+    int reads = -2;   // -2 nothing, -1 a linear predictor, >= 0 the variable
+    each_operand(f, 0, [&](const nuts_operand& o) {
+      if (reads != -2) return;
+      if (o.kind == NUTS_OP_VAR || o.kind == NUTS_OP_GATHER) reads = o.ref;
+      else if (o.kind == NUTS_OP_LIN) reads = -1;
+    });
+    if (reads != -2)
+      return refuse_prior("Potential factor " + std::to_string(fi) + " reads " + (reads >= 0 ? "variable " + std::to_string(reads) : std::string("a linear predictor")) +
+                          ": it reweights the prior");
+  }
+  std::vector<int> prior_of(nv, -1);
+  for (int k = 0; k < nv; ++k) {
+    const nuts_var& v = s->vars[k];
+    const std::string who = "variable " + std::to_string(k);
+    if (k > PRIOR_INDEX_MAX) return refuse_prior(who + ": its index does not fit the 14 bits the counter gives it");
+    // the prior: the ONE factor over the bare variable, of its size, of a family prior_family_ok accepts; `other`: the first factor
+    // over the bare variable that fails on its family alone.  (The engine is not told which factors are OBSERVED, and the host layer
+    // leaves those out: an observed factor's argument 0 is a data operand, never a bare variable, so it cannot be counted here.)
+    int found = -1, count = 0, other = -1;
+    for (int fi = 0; fi < nf; ++fi) {
+      const nuts_factor& f = s->factors[fi];
+      const nuts_term& t = f.arg[0];
+      const bool bare = f.nargs >= 1 && t.a.kind == NUTS_OP_VAR && t.a.ref == k && t.b.kind == NUTS_OP_CONST && t.b.c == 0.0 && t.c.kind == NUTS_OP_CONST && t.c.c == 0.0;
+      if (!bare || f.size != v.size) continue;
+      if (prior_family_ok(f.dist)) { if (count++ == 0) found = fi; }
+      else if (other < 0) other = fi;
+    }
+    if (count == 0 && other < 0 && s->mix_N > 0 && s->mix_w_simplex && s->mix_w_logits == k && v.size == s->mix_K - 1 && s->mix_K <= PRIOR_MAXK) continue;   // the node's Dirichlet weights
+    if (count == 0 && other >= 0) {
+      const int dist = s->factors[other].dist;
+      if (!pp_family_ok(dist)) return refuse_prior(who + ": its prior is a " + prior_family_name(dist) + " factor: forward sampling of that family is out of scope");
+      return refuse_prior(who + ": its prior is a discrete " + prior_family_name(dist) + " factor");
+    }
+    if (count == 0) return refuse_prior(who + " has no prior factor (a prior lowered op by op into a program or a Potential cannot be drawn from)");
+    if (count > 1) return refuse_prior(who + " has more than one prior factor");
+    const nuts_factor& f = s->factors[found];
+    bool lin = false;
+    each_operand(f, 1, [&](const nuts_operand& o) { lin = lin || o.kind == NUTS_OP_LIN; });
+    if (lin) return refuse_prior(who + ": its prior reads a linear predictor or a derived vector");
+    if (v.offset < 0 || v.offset + v.size > m->md.n) return refuse_prior(who + " lies outside the position vector");
+    prior_of[k] = found;
+  }
+  std::vector<int> level(nv, -1);
+  for (int done = 0, round = 0; done < nv; ++round) {
+    if (round > nv) return refuse_prior("the priors read each other in a cycle");
+    for (int k = 0; k < nv; ++k) {
+      if (level[k] >= 0) continue;
+      int lv = 0;
+      if (prior_of[k] >= 0)
+        each_operand(s->factors[prior_of[k]], 1, [&](const nuts_operand& o) {
+          if (o.kind != NUTS_OP_VAR && o.kind != NUTS_OP_GATHER) return;
+          if (o.ref < 0 || o.ref >= nv || o.ref == k || level[o.ref] < 0 || lv < 0) lv = -1;
+          else lv = std::max(lv, level[o.ref] + 1);
+        });
+      if (lv >= 0) { level[k] = -2 - lv; }   // (resolved in this round: visible to the others from the next one)
+    }
+    int now = 0;
+    for (int k = 0; k < nv; ++k) {
+      if (level[k] <= -2) { level[k] = -2 - level[k]; ++now; }
+    }
+    if (now == 0) return refuse_prior("the priors read each other in a cycle");
+    done += now;
+  }
+  const int depth = 1 + *std::max_element(level.begin(), level.end());
+  m->prior_levels.assign(depth, {});
+  for (int k = 0; k < nv; ++k) {
+    const nuts_var& v = s->vars[k];
+    std::vector<PriorVar>& L = m->prior_levels[level[k]];
+    PriorVar pv{};
+    pv.factor = prior_of[k]; pv.index = k; pv.offset = v.offset; pv.size = v.size; pv.transform = v.transform;
+    pv.lower = v.lower; pv.upper = v.upper;
+    pv.start = L.empty() ? 0 : L.back().start + (L.back().factor < 0 ? 1 : L.back().size);
+    L.push_back(pv);
+  }
+}
+
+extern "C" int nuts_model_prior(nuts_model* m, int64_t S, uint64_t seed, int64_t draw0, double* q_out, int64_t* n_nonfinite) {
+  if (!m) { g_err = "null argument"; return NUTS_E_ARG; }
+  if (m->group) { g_err = "prior predictive: the model is a member of a chain group (its stream is the group's); remove the chain first"; return NUTS_E_ARG; }
+  if (!m->prior_err.empty()) { g_err = "prior predictive: " + m->prior_err; return NUTS_E_ARG; }
+  if (S < 0 || (S > 0 && !q_out)) { g_err = "null argument"; return NUTS_E_ARG; }
+  if (draw0 < 0 || draw0 > ((int64_t)1 << 32) - S) { g_err = "prior predictive: draw numbers must stay below 2^32"; return NUTS_E_ARG; }
+  const ModelDev& md = m->md;
+  const int n = md.n;
+  const int B = std::min(std::max(env_int("NUTS_PRIOR_B", PRIOR_B), 1), PRIOR_B);
+  if (!m->prior_tab) {
+    std::vector<PriorVar> all;
+    for (const auto& L : m->prior_levels) all.insert(all.end(), L.begin(), L.end());
+    HIPCHK(hipMalloc((void**)&m->prior_tab, std::max<size_t>(all.size(), 1) * sizeof(PriorVar)));
+    HIPCHK(hipMemcpy(m->prior_tab, all.data(), all.size() * sizeof(PriorVar), hipMemcpyHostToDevice));
+  }
+  if (!m->prior_q) HIPCHK(hipMalloc((void**)&m->prior_q, (size_t)PRIOR_B * std::max(n, 1) * sizeof(double)));
+  const PPKey key = pp_key(seed);
+  for (int64_t s0 = 0; s0 < S; s0 += B) {
+    const int nb = (int)std::min<int64_t>(B, S - s0);
+    HIPCHK(hipMemsetAsync(m->prior_q, 0, (size_t)nb * n * sizeof(double), m->stream));   // (a factor's argument 0, its own variable, is read before it is drawn)
+    size_t at = 0;
+    for (const auto& L : m->prior_levels) {
+      const int total = L.back().start + (L.back().factor < 0 ? 1 : L.back().size);
+      hipLaunchKernelGGL(k_prior_level, dim3((unsigned)((total + PRIOR_BLOCK - 1) / PRIOR_BLOCK), nb), dim3(PRIOR_BLOCK), 0, m->stream, md, m->prior_q,
+                         (const PriorVar*)(m->prior_tab + at), (int)L.size(), total, key, (uint32_t)(draw0 + s0));
+      at += L.size();
+    }
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(q_out + (size_t)s0 * n, m->prior_q, (size_t)nb * n * sizeof(double), hipMemcpyDeviceToHost, m->stream));
+    HIPCHK(hipStreamSynchronize(m->stream));
+  }
+  if (n_nonfinite) {   // counted on the host copy: reported, not hidden
+    int64_t bad = 0;
+    for (int64_t k = 0; k < S * n; ++k) bad += std::isfinite(q_out[k]) ? 0 : 1;
+    *n_nonfinite = bad;
+  }
   return NUTS_OK;
 }
 

@@ -11,6 +11,10 @@ predictive mean and sd) weights the replicates by the Pareto-smoothed leave-one-
 The generator is counter-based: the value of (draw s, observation i) of a variable depends on (seed, variable, s, i) and on the
 variable's parameters at draw s, never on how the draws were batched or split over calls.  s is the GLOBAL draw index: draw d of the model's
 chain number c is c * draws + d, whichever process holds that chain.  The draws are what `sample()` returns: raveled, UNCONSTRAINED positions.
+
+`sample_prior_predictive` / `prior_ppc` (`pm.sample_prior_predictive`) put one step in front of all this: the positions themselves are
+drawn from the priors of the free variables, in ancestral order on the device (csrc/prior.h, csrc/prior_kernel.h), and then take the
+same path.
 """
 
 from __future__ import annotations
@@ -228,3 +232,193 @@ def loo_pit(model, draws, *, var_name: Optional[str] = None, reff: float = 1.0, 
     cols = [loglik.caller_order(spec, node[1], a) for a in cols]
     elpd_i, khat, lppd_i = (loglik.caller_order(spec, node[1], a) for a in (elpd_i, khat, lppd_i))
     return loo_pit_from_accumulators(*cols, elpd_i, khat, lppd_i, n_draws, pointwise=pointwise)
+
+
+# ---- prior predictive ----------------------------------------------------------------------------------------------------------------
+# `pm.sample_prior_predictive` draws the free variables from their priors, then the data given them.  The first half is the engine's
+# `nuts_model_prior` (csrc/prior.h, csrc/prior_kernel.h): S unconstrained positions in ancestral order; the second half is the
+# posterior-predictive path above, unchanged, fed with those positions.  `prior_refusal` / `prior_plan` restate the engine's plan
+# builder (csrc/engine.hip `prior_build_plan`) on the host, rule by rule and in its order, as `refusal` restates `pp_check`.
+PRIOR_INDEX_MAX = 0x3FFF
+PRIOR_DISCRETE = (ms.D_BERNOULLI, ms.D_BERNOULLI_LOGIT, ms.D_POISSON)
+PRIOR_SAMPLES = 500      # `pm.sample_prior_predictive`'s default number of draws
+PRIOR_BATCH = 64         # draws `prior_ppc` asks the engine for at a time (the engine's own batch, csrc/engine.hip PRIOR_B)
+
+
+def _operands(f, first_arg: int = 0):
+    for t in f.args[first_arg:]:
+        yield from (t.a, t.b, t.c)
+    for ins in (getattr(f, "prog", ()) or ()):
+        yield from (ins.x, ins.y, ins.z)
+
+
+def _prior_analysis(spec):
+    """-> (why, levels): the reason the prior of `spec` cannot be drawn from (then levels is None), or None and the ancestral order."""
+    who = lambda k: f"variable {k} ({spec.vars[k].name!r})"   # noqa: E731
+    if spec.mvnormal is not None:
+        k = spec.mvnormal.var
+        return f"{who(k)} is the MvNormal node's: its prior draw needs a Cholesky factor on the device", None
+    mix = getattr(spec, "mixture_rows", None)
+    if mix is not None and mix.assign is not None:
+        return f"{mix.name!r} is a conditional mixture: its assignments are another step method's", None
+    for fi, f in enumerate(spec.factors):
+        if f.dist != ms.D_POTENTIAL:
+            continue
+        for o in _operands(f):
+            if o.kind in (ms.OP_VAR, ms.OP_GATHER):
+                return f"Potential factor {fi} ({f.name!r}) reads {who(o.ref)}: it reweights the prior", None
+            if o.kind == ms.OP_LIN:
+                return f"Potential factor {fi} ({f.name!r}) reads a linear predictor: it reweights the prior", None
+    prior_of = {}
+    bare: Dict[int, list] = {}       # variable -> the non-observed factors over the bare variable
+    for fi, f in enumerate(spec.factors):
+        t = f.args[0] if f.args else None
+        if t is not None and not getattr(f, "observed", False) and t.a.kind == ms.OP_VAR and t.b == ms.ZERO and t.c == ms.ZERO:
+            bare.setdefault(t.a.ref, []).append(fi)
+    for k, v in enumerate(spec.vars):
+        if k > PRIOR_INDEX_MAX:
+            return f"{who(k)}: its index does not fit the 14 bits the counter gives it", None
+        over = [fi for fi in bare.get(k, ()) if spec.factors[fi].size == v.size]
+        found = [fi for fi in over if spec.factors[fi].dist not in REFUSED_FAMILIES + PRIOR_DISCRETE]
+        if not over and mix is not None and mix.w_alpha is not None and mix.w_logits == k and getattr(v, "simplex", False):
+            prior_of[k] = -1        # the mixture node's Dirichlet weights: the node owns the prior
+            continue
+        if not found and over:      # a factor over the bare variable that fails on its family alone
+            dist = spec.factors[over[0]].dist
+            if dist in REFUSED_FAMILIES:
+                return f"{who(k)}: its prior is a {ms.DIST_NAMES[dist]} factor: forward sampling of that family is out of scope", None
+            return f"{who(k)}: its prior is a discrete {ms.DIST_NAMES[dist]} factor", None
+        if not found:
+            return f"{who(k)} has no prior factor (a prior lowered op by op into a program or a Potential cannot be drawn from)", None
+        if len(found) > 1:
+            return f"{who(k)} has more than one prior factor", None
+        f = spec.factors[found[0]]
+        if any(o.kind == ms.OP_LIN for o in _operands(f, 1)):
+            return f"{who(k)}: its prior reads a linear predictor or a derived vector", None
+        prior_of[k] = found[0]
+    level: Dict[int, int] = {}
+    while len(level) < len(spec.vars):
+        new = {}
+        for k in range(len(spec.vars)):
+            if k in level:
+                continue
+            parents = set() if prior_of[k] < 0 else {o.ref for o in _operands(spec.factors[prior_of[k]], 1) if o.kind in (ms.OP_VAR, ms.OP_GATHER)}
+            if k not in parents and all(p in level for p in parents):
+                new[k] = 1 + max((level[p] for p in parents), default=-1)
+        if not new:
+            return "the priors read each other in a cycle", None
+        level.update(new)
+    levels = [[] for _ in range(1 + max(level.values(), default=-1))]
+    for k, v in enumerate(spec.vars):
+        levels[level[k]].append((v.name, prior_of[k]))
+    return None, levels
+
+
+def prior_refusal(spec) -> Optional[str]:
+    """Why S positions cannot be drawn from the priors of `spec`'s free variables, or None.  A free variable has a samplable prior
+    when exactly one non-observed factor has the bare variable as its value, the variable's size and a continuous family
+    `refusal` accepts; the weights of the mixture node under `w ~ Dirichlet` are the node's own."""
+    return _prior_analysis(spec)[0]
+
+
+def prior_plan(spec):
+    """The ancestral order of `spec`'s free variables: a list of levels, each a list of (variable name, index of its prior factor;
+    -1 for the mixture node's Dirichlet weights).  level(v) = 1 + the largest level of the variables v's prior reads, 0 when it
+    reads none.  Raises ValueError where `prior_refusal` gives a reason."""
+    why, levels = _prior_analysis(spec)
+    if why:
+        raise ValueError("prior predictive refused: " + why)
+    return levels
+
+
+def constrained_from_positions(spec, q: np.ndarray) -> Dict[str, np.ndarray]:
+    """q (chains, draws, n) -> {name: (chains, draws, *shape)}: the trace's backward transform of the variables (`trace.posterior`)
+    and the spec's Deterministics (`trace.deterministics`, what the trace backend records), in that order."""
+    from pymc_amd import trace
+
+    out = trace.posterior(spec, q)
+    for name, val in trace.deterministics(spec, q.reshape(-1, spec.n)).items():
+        out[name] = val.reshape(q.shape[:2] + val.shape[1:])
+    return out
+
+
+def sample_prior_predictive(model, samples: int = PRIOR_SAMPLES, *, var_names=None, random_seed=0, device: Optional[int] = None, func=None) -> dict:
+    """`pm.sample_prior_predictive`: `samples` draws of the free variables from their priors, in ancestral order on the device, and one
+    replicate of every observed variable at each of them.  Returns
+
+      "q"                  (1, S, n) the raveled UNCONSTRAINED positions -- everything below is a function of them
+      "prior"              {variable: (1, S, *constrained shape)}: the trace's backward transform of q, Deterministics included --
+                           exactly the values the likelihood kernels saw
+      "prior_predictive"   {observed variable: (1, S, size)} = `sample_posterior_predictive(model, q, random_seed=..., chain_ids=[0])`
+      "n_nonfinite"        non-finite entries of q (a draw on the boundary of its support, invalid parameters): reported, not hidden
+
+    `random_seed`: the generator's 64-bit key, shared by both halves (their streams never coincide: csrc/prior.h).  `var_names`
+    restricts both dicts to the names given.  A model whose observed variables the posterior predictive refuses still gets q and
+    prior: the reason is under "prior_predictive_refused" and prior_predictive is {}.  A refused prior raises ValueError."""
+    spec = loglik._spec_of(model)
+    why = prior_refusal(spec)
+    if why:
+        raise ValueError("prior predictive refused: " + why)
+    S = int(samples)
+    if S < 0:
+        raise ValueError("samples must not be negative")
+    observed = [nd[0] for nd in ms.observed_nodes(spec)]
+    names = None if var_names is None else ([var_names] if isinstance(var_names, str) else list(var_names))
+    f, own = loglik._function(spec, device, func)
+    try:
+        q, bad = f.prior(S, seed=random_seed, draw0=0)
+        q = q[None]
+        prior = constrained_from_positions(spec, q)
+        if names is not None:
+            missing = [v for v in names if v not in prior and v not in observed]
+            if missing:
+                raise KeyError(f"not variables of the model: {missing}")
+            prior = {k: v for k, v in prior.items() if k in names}
+        out = {"q": q, "prior": prior, "prior_predictive": {}, "n_nonfinite": bad}
+        wanted = observed if names is None else [v for v in names if v in observed]
+        nodes = loglik._select(spec, wanted)
+        pp_why = refusal(spec, nodes) if nodes else None
+        if pp_why:
+            out["prior_predictive_refused"] = pp_why
+        elif nodes:
+            out["prior_predictive"] = sample_posterior_predictive(spec, q, var_names=wanted, random_seed=random_seed, chain_ids=[0], func=f)
+        return out
+    finally:
+        if own:
+            f.close()
+
+
+def prior_ppc(model, samples: int = PRIOR_SAMPLES, *, var_name: Optional[str] = None, random_seed=0, pointwise: bool = False,
+              device: Optional[int] = None, func=None, batch: int = PRIOR_BATCH) -> dict:
+    """Streaming prior-predictive checks of one observed variable (see `ppc_from_accumulators`): the positions are drawn from the
+    priors `batch` at a time and fed to the accumulators of `ppc`; neither the S positions nor the draws x observations matrix is
+    held.  The replicates are those `sample_prior_predictive` returns under the same `random_seed`, whatever `batch` is."""
+    spec = loglik._spec_of(model)
+    why = prior_refusal(spec)
+    if why:
+        raise ValueError("prior predictive refused: " + why)
+    nodes = ms.observed_nodes(spec)
+    why = loglik.refusal(spec, [])
+    if why:
+        raise ValueError("posterior predictive refused: " + why)
+    if not nodes:
+        raise ValueError("the model has no observed variable")
+    if var_name is None and len(nodes) > 1:
+        raise TypeError(f"Found several observed variables {[nd[0] for nd in nodes]}, var_name cannot be None")
+    node = _nodes_or_refuse(spec, var_name)[0]
+    S, step = int(samples), max(int(batch), 1)
+    f, own = loglik._function(spec, device, func)
+    try:
+        acc = f.ppc_accumulator(node[0], seed=random_seed, node=(node[1], node[2]))
+        try:
+            for s0 in range(0, S, step):
+                acc.update(f.prior(min(step, S - s0), seed=random_seed, draw0=s0)[0])
+            mean_i, var_i, n_lt, n_eq, n_draws = acc.read()
+            T, T_obs = acc.stats()
+        finally:
+            acc.close()
+    finally:
+        if own:
+            f.close()
+    mean_i, var_i, n_lt, n_eq = (loglik.caller_order(spec, node[1], a) for a in (mean_i, var_i, n_lt, n_eq))
+    return ppc_from_accumulators(mean_i, var_i, n_lt, n_eq, T, T_obs, n_draws, pointwise=pointwise)

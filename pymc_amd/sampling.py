@@ -549,6 +549,7 @@ def sample(
     posterior_predictive: bool = False,
     summary: bool = False,
     loo_pit: bool = False,
+    prior_predictive=False,
     **step_kwargs,
 ):
     """Reduced `pm.sample` (mcmc.py:620-1190) returning raw arrays (and, with ``return_multitrace=True``, the reference's
@@ -600,6 +601,11 @@ def sample(
     the dict of `pymc_amd.predictive.loo_pit`} from two streamed passes over the draws the result holds, with the key and the draw
     numbering of ``posterior_predictive``; a rank left with no draws gets none.  Refused before sampling where
     ``posterior_predictive`` is.
+
+    ``prior_predictive`` (`pm.sample_prior_predictive`; True: 500 draws, or their number): ``result["prior"]`` = {variable: (1, S,
+    *shape)} drawn from the priors in ancestral order on the device and ``result["prior_predictive"]`` = {observed variable: (1, S,
+    size)}, one replicate at each of them (`pymc_amd.predictive.sample_prior_predictive`, under the key of
+    ``posterior_predictive``).  A model whose prior cannot be drawn from is refused before sampling.
     """
     rank, world, local = _dist_info()
     from pymc_amd.lowering import as_model_spec
@@ -623,6 +629,12 @@ def sample(
         why = pp_refusal(spec)
         if why:
             raise ValueError("loo_pit=True refused: " + why)
+    if prior_predictive is not False and prior_predictive is not None:
+        from pymc_amd.predictive import prior_refusal
+
+        why = prior_refusal(spec)
+        if why:
+            raise ValueError("prior_predictive=True refused: " + why)
     if device is None and world > 1:
         device = local
     # mcmc.py:907-908 -- every rank derives ALL chain generators so chain c is the same stream on any layout
@@ -890,6 +902,13 @@ def sample(
         result["loo_pit"] = {nd[0]: loo_pit_of_trace(spec, result["draws"], var_name=nd[0], random_seed=seed_from(random_seed), chain_ids=result["chains"],
                                                      device=device, func=f if hasattr(f, "loo_pit_accumulator") else None)
                              for nd in observed_nodes(spec)}
+    if prior_predictive is not False and prior_predictive is not None:
+        from pymc_amd.predictive import PRIOR_SAMPLES, sample_prior_predictive, seed_from
+
+        f = getattr(step, "_logp_dlogp_func", None)
+        pr = sample_prior_predictive(spec, PRIOR_SAMPLES if prior_predictive is True else int(prior_predictive), random_seed=seed_from(random_seed),
+                                     device=device, func=f if hasattr(f, "prior") else None)
+        result["prior"], result["prior_predictive"] = pr["prior"], pr["prior_predictive"]
     if summary and result["draws"] is not None and np.shape(result["draws"])[0] > 0:
         from pymc_amd.summary import summary as summarize_trace
 

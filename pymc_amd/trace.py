@@ -48,6 +48,35 @@ def posterior(spec: ModelSpec, draws: np.ndarray, include_transformed: bool = Fa
     return out
 
 
+def deterministic_shape(spec: ModelSpec, name: str) -> tuple:
+    """Shape of `pm.Deterministic` `name` in the trace: the recorded one, else () for one element and (size,) for a vector."""
+    size = spec.deterministics[name][2]
+    return tuple(getattr(spec, "deterministic_shapes", {}).get(name, () if size == 1 else (size,)))
+
+
+def deterministics(spec: ModelSpec, positions: np.ndarray, names=None) -> Dict[str, np.ndarray]:
+    """The spec's Deterministics at K raveled UNCONSTRAINED positions (K, n) -> {name: (K, *shape)}: host arithmetic
+    (`model_spec.eval_program`) at the backward-transformed values.  The one evaluation the trace backend and the prior predictive
+    share."""
+    from pymc_amd.model_spec import eval_program
+
+    positions = np.asarray(positions, dtype="float64")
+    x = np.empty_like(positions)                    # constrained values, spec layout
+    for v in spec.vars:
+        blk = positions[:, v.offset : v.offset + v.size]
+        # (a simplex-transformed variable has K constrained elements for its K - 1 stored ones: no slot in this layout.  No
+        # Deterministic can refer to it -- the lowering leaves such a one out of the trace with a warning, `ModelBuilder` has no
+        # operand for it -- so its block keeps the stored values)
+        x[:, v.offset : v.offset + v.size] = blk if getattr(v, "simplex", False) else backward(v, blk)
+    out: Dict[str, np.ndarray] = {}
+    for nm, (prog, term, size) in getattr(spec, "deterministics", {}).items():
+        if names is not None and nm not in names:
+            continue
+        val = eval_program(spec, prog, term, x)
+        out[nm] = np.array(np.broadcast_to(val, (len(positions), size))).reshape((len(positions), *deterministic_shape(spec, nm)))
+    return out
+
+
 def sample_stats(stats: List[List[dict]]) -> Dict[str, np.ndarray]:
     """Per-chain lists of per-draw stat dicts -> {stat: (chains, draws)}; the `warning` objects stay a nested list."""
     keys = [k for k in stats[0][0] if k != "warning"]

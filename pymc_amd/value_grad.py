@@ -268,6 +268,16 @@ class DeviceValueGradFunction:
         _lib.check(rc, "nuts_model_predictive")
         return out
 
+    def prior(self, S: int, seed: int = 0, draw0: int = 0):
+        """S raveled UNCONSTRAINED positions drawn from the priors of the free variables, in ancestral order (`nuts_model_prior`)
+        -> (q [S, n], number of non-finite entries of q).  Draw s of the call is draw `draw0 + s` of the generator's stream under
+        `seed`; the result does not depend on how S is split over calls."""
+        out = np.empty((int(S), self.n))
+        bad = C.c_int64()
+        rc = _lib.load().nuts_model_prior(self._handle, int(S), int(seed) & 0xFFFFFFFFFFFFFFFF, int(draw0), _lib.dptr(out), C.byref(bad))
+        _lib.check(rc, "nuts_model_prior")
+        return out, int(bad.value)
+
     def ppc_accumulator(self, name: str, seed: int = 0, node=None) -> "PpcAccumulator":
         """Device-resident streaming predictive checks of observed variable `name` (`nuts_ppc_*`)."""
         kind, index = self._ll_node(name, node)
