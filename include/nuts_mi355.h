@@ -465,6 +465,32 @@ int64_t nuts_summary_max_draws(void);
 int nuts_summary(const double *x /* host [C][N][P] */, int64_t C, int64_t N, int64_t P, double hdi_prob,
                  double *out /* host [NUTS_SUMMARY_COLS][P] */);
 
+/* ---- power-scaling sensitivity: `az.psens`, the `priorsense` table -------------------------------------------------------------------
+ * How far the posterior of each parameter moves when the prior or the likelihood is raised to a power next to 1 (Kallioinen, Paananen,
+ * Buerkner, Vehtari 2023); pymc_amd/csrc/psens.h holds the definitions, DESIGN.md 4.23 the layout.
+ *   nuts_model_logdens_sum: the total over the N values nuts_model_loglik(m, kind, index, ...) gives for each of the S draws, reduced on
+ *                           the device -- the [S][N] matrix never reaches the host.  Accepts and refuses what nuts_model_loglik does; a
+ *                           prior factor is a NUTS_LL_FACTOR index like any other (a factor's term holds no Jacobian of a transform).
+ *                           Fixed-order partial sums, no atomics: a draw's total does not depend, bit for bit, on the option NUTS_LL_B, on
+ *                           how the draws are split over calls or on the other draws.  A row holding -inf gives -inf, a NaN gives NaN.
+ *   nuts_psens_weights:     the S normalised Pareto-smoothed importance weights of scaling a component with log-density lc[s] by the
+ *                           power alpha: PSIS (csrc/psis.h, reff = 1, tied values share the mean weight of their ranks) of the one
+ *                           column (1 - alpha) lc, divided by their sum, and the Pareto shape khat.  A tail of 4 values or fewer is
+ *                           not smoothed: khat = +inf and the normalised raw ratios.  A non-finite lc: every weight and khat NaN.
+ *   nuts_psens:             per parameter cjs_lo, cjs_hi (the cumulative Jensen-Shannon distance between the draws' ECDF and their
+ *                           ECDF under w_lo / w_hi, the larger of x and -x) and sensitivity = (cjs_lo + cjs_hi) / (2 log2(1 + delta)).
+ *                           A constant parameter and one with a non-finite draw have NaN in every column.  P is processed in blocks
+ *                           of the option NUTS_PSENS_BLOCK (1024) parameters, read at every call; a parameter's row depends on its
+ *                           own draws and the two weight vectors only, bit for bit, and does not change when the draws are permuted
+ *                           together with their weights.
+ * The last two run on the current device (nuts_set_device) and need no model.  One workgroup sorts the S draws in LDS:
+ * S > nuts_summary_max_draws() = 8192, S < 2, P < 1, delta <= 0 and alpha <= 0 are NUTS_E_ARG with a text in nuts_last_error(). */
+#define NUTS_PSENS_COLS 3   /* cjs_lo cjs_hi sensitivity */
+int nuts_model_logdens_sum(nuts_model *m, int32_t kind, int32_t index, const double *q, int64_t S, double *out /* host [S] */);
+int nuts_psens_weights(const double *lc /* host [S] */, int64_t S, double alpha, double *w /* host [S] */, double *khat);
+int nuts_psens(const double *x /* host [S][P], parameters fastest */, int64_t S, int64_t P, const double *w_lo, const double *w_hi,
+               double delta, double *out /* host [NUTS_PSENS_COLS][P] */);
+
 /* ---- model comparison: `az.compare` on the log scale ----------------------------------------------------------------------------------
  * K models over the same N observations, each given by its pointwise elpd (loo_i of nuts_psis_read, waic_i of nuts_waic_read): the
  * elpd of every model with its standard error, the standard error of its difference to the best one, and the model weights by

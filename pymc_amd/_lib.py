@@ -308,6 +308,9 @@ SYMBOLS = {
     "nuts_loo_pit_destroy": (None, [_VP]),
     "nuts_summary_max_draws": (C.c_int64, []),
     "nuts_summary": (C.c_int, [_PD, C.c_int64, C.c_int64, C.c_int64, C.c_double, _PD]),
+    "nuts_model_logdens_sum": (C.c_int, [_VP, C.c_int32, C.c_int32, _PD, C.c_int64, _PD]),
+    "nuts_psens_weights": (C.c_int, [_PD, C.c_int64, C.c_double, _PD, _PD]),
+    "nuts_psens": (C.c_int, [_PD, C.c_int64, C.c_int64, _PD, _PD, C.c_double, _PD]),
     "nuts_compare_create": (_VP, [C.c_int64, C.c_int32]),
     "nuts_compare_set": (C.c_int, [_VP, C.c_int32, _PD, C.POINTER(C.c_int64)]),
     "nuts_compare_moments": (C.c_int, [_VP, _PD, _PD, _PD, C.POINTER(C.c_int32)]),

@@ -29,6 +29,7 @@
 #include "prior_kernel.h"
 #include "loo_pit_kernel.h"
 #include "summary_kernel.h"
+#include "psens_kernel.h"
 #include "compare_kernel.h"
 #include "nuts_mi355.h"
 #include "pcg64_stream.h"
@@ -214,6 +215,8 @@ struct nuts_model {
   double *ll_q = nullptr, *ll_stage = nullptr, *ll_par = nullptr, *ll_sc = nullptr, *ll_lfact = nullptr;   // (ll_lfact: factln(y) per row of a Poisson GLM node)
   int32_t* ll_dead = nullptr;
   int64_t ll_stage_n = 0, ll_par_n = 0;
+  double *ld_part = nullptr, *ld_tot = nullptr;   // nuts_model_logdens_sum: the partials of a batch [LL_B][ld_part_n], the totals of a call [ld_tot_n]
+  int64_t ld_part_n = 0, ld_tot_n = 0;
   int n_waic = 0;                  // live nuts_waic / nuts_psis / nuts_ppc handles on this model
   // prior draws (prior_kernel.h): the ancestral order as levels of variables, or why the model has none (prior_build_plan, when the
   // model is created); the levels' tables on the device one after the other and ONE batch of positions [PRIOR_B][n], allocated when
@@ -2156,7 +2159,7 @@ extern "C" void nuts_model_destroy(nuts_model* m) {
   if (m->group) group_remove_model(m->group, m);
   for (void* p : m->owned) if (p) hipFree(p);
   for (void* p : {(void*)m->ll_q, (void*)m->ll_stage, (void*)m->ll_par, (void*)m->ll_sc, (void*)m->ll_dead, (void*)m->ll_lfact, (void*)m->prior_tab,
-                  (void*)m->prior_q}) if (p) hipFree(p);
+                  (void*)m->prior_q, (void*)m->ld_part, (void*)m->ld_tot}) if (p) hipFree(p);
   for (auto e : m->ev) hipEventDestroy(e);
   if (m->host_pin) hipHostFree(m->host_pin);
   if (m->own_stream) hipStreamDestroy(m->own_stream);
@@ -3167,6 +3170,116 @@ extern "C" int nuts_summary(const double* x, int64_t C, int64_t N, int64_t P, do
   if (xt) hipFree(xt);
   if (res) hipFree(res);
   HIPCHK_RET(e, "nuts_summary", NUTS_E_HIP);
+  return NUTS_OK;
+}
+
+// ---- power-scaling sensitivity (psens.h, psens_kernel.h) ----------------------------------------------------------------
+// nuts_model_logdens_sum: the route of nuts_model_loglik, with the [nb][N] block reduced per draw where it lies; S doubles come back.
+static_assert(NUTS_PSENS_COLS == PS_COLS, "psens.h restates the column count of nuts_mi355.h");
+
+extern "C" int nuts_model_logdens_sum(nuts_model* m, int32_t kind, int32_t index, const double* q, int64_t S, double* out) {
+  int64_t N = 0;
+  if (const int rc = ll_check(m, kind, index, &N)) return rc;
+  if (S < 0 || (S > 0 && (!q || !out))) { g_err = "null argument"; return NUTS_E_ARG; }
+  if (S == 0) return NUTS_OK;
+  if (const int rc = ll_ensure(m, kind, N)) return rc;
+  const int B = ll_batch(), G = ld_groups(N);
+  // both buffers stay with the model and only grow; the stream orders a batch's upload and kernels behind the batch before, so the
+  // host waits once, for the totals
+  if (m->ld_part_n < G) {
+    HIPCHK(hipStreamSynchronize(m->stream));
+    if (m->ld_part) hipFree(m->ld_part);
+    m->ld_part = nullptr; m->ld_part_n = 0;
+    HIPCHK(hipMalloc((void**)&m->ld_part, (size_t)LL_B * G * sizeof(double)));
+    m->ld_part_n = G;
+  }
+  if (m->ld_tot_n < S) {
+    HIPCHK(hipStreamSynchronize(m->stream));
+    if (m->ld_tot) hipFree(m->ld_tot);
+    m->ld_tot = nullptr; m->ld_tot_n = 0;
+    HIPCHK(hipMalloc((void**)&m->ld_tot, (size_t)S * sizeof(double)));
+    m->ld_tot_n = S;
+  }
+  for (int64_t s0 = 0; s0 < S; s0 += B) {
+    const int nb = (int)std::min<int64_t>(B, S - s0);
+    if (const int rc = ll_eval_batch(m, kind, index, q + (size_t)s0 * m->md.n, nb, N, B)) return rc;
+    hipLaunchKernelGGL(k_logdens_sum, dim3((unsigned)G, (unsigned)nb), dim3(PS_BLOCK), 0, m->stream, (const double*)m->ll_stage, N, m->ld_part);
+    hipLaunchKernelGGL(k_logdens_finish, dim3((unsigned)nb), dim3(PS_BLOCK), 0, m->stream, (const double*)m->ld_part, G, m->ld_tot + s0);
+  }
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(out, m->ld_tot, (size_t)S * sizeof(double), hipMemcpyDeviceToHost, m->stream));
+  HIPCHK(hipStreamSynchronize(m->stream));
+  return NUTS_OK;
+}
+
+static int psens_args(const char* who, int64_t S) {
+  if (S < 2) { g_err = std::string(who) + ": at least 2 draws"; return NUTS_E_ARG; }
+  if (S > PS_MAX_S) {
+    g_err = std::string(who) + ": " + std::to_string(S) + " draws exceed the " + std::to_string(PS_MAX_S) +
+            " draws one workgroup sorts in LDS (nuts_summary_max_draws); a larger trace is out of scope";
+    return NUTS_E_ARG;
+  }
+  return NUTS_OK;
+}
+
+extern "C" int nuts_psens_weights(const double* lc, int64_t S, double alpha, double* w, double* khat) {
+  if (const int rc = psens_args("nuts_psens_weights", S)) return rc;
+  if (!(alpha > 0.0) || !(alpha - alpha == 0.0)) { g_err = "nuts_psens_weights: alpha must be positive and finite"; return NUTS_E_ARG; }
+  if (!lc || !w || !khat) { g_err = "null argument"; return NUTS_E_ARG; }
+  if (nuts_device_count() < 1) { g_err = "no HIP device visible: nuts_psens_weights requires an MI355X (gfx950); there is no CPU fallback"; return NUTS_E_HIP; }
+  const int K1 = (int)psis_tail_len(S, 1.0) + 1;
+  double* dl = dev_alloc<double>((size_t)S);
+  double* dw = dev_alloc<double>((size_t)S + 1);   // the weights, then khat
+  hipError_t e = dl && dw ? hipSuccess : hipErrorOutOfMemory;
+  if (e == hipSuccess) e = hipMemcpy(dl, lc, (size_t)S * sizeof(double), hipMemcpyHostToDevice);
+  if (e == hipSuccess) {
+    hipLaunchKernelGGL(k_psens_weights, dim3(1), dim3(PS_BLOCK), 0, 0, (const double*)dl, (int)S, alpha, K1, dw, dw + S);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipStreamSynchronize(0);
+  std::vector<double> host((size_t)S + 1);
+  if (e == hipSuccess) e = hipMemcpy(host.data(), dw, ((size_t)S + 1) * sizeof(double), hipMemcpyDeviceToHost);
+  if (dl) hipFree(dl);
+  if (dw) hipFree(dw);
+  HIPCHK_RET(e, "nuts_psens_weights", NUTS_E_HIP);
+  std::copy(host.begin(), host.begin() + S, w);
+  *khat = host[(size_t)S];
+  return NUTS_OK;
+}
+
+extern "C" int nuts_psens(const double* x, int64_t S, int64_t P, const double* w_lo, const double* w_hi, double delta, double* out) {
+  if (const int rc = psens_args("nuts_psens", S)) return rc;
+  if (P < 1) { g_err = "nuts_psens: at least 1 parameter"; return NUTS_E_ARG; }
+  if (!(delta > 0.0) || !(delta - delta == 0.0)) { g_err = "nuts_psens: delta must be positive and finite"; return NUTS_E_ARG; }
+  if (!x || !w_lo || !w_hi || !out) { g_err = "null argument"; return NUTS_E_ARG; }
+  if (nuts_device_count() < 1) { g_err = "no HIP device visible: nuts_psens requires an MI355X (gfx950); there is no CPU fallback"; return NUTS_E_HIP; }
+  const int64_t blk = env_int("NUTS_PSENS_BLOCK", 1024);
+  if (blk < 1) { g_err = "NUTS_PSENS_BLOCK must be at least 1"; return NUTS_E_ARG; }
+  const int64_t B = std::min(P, blk);
+  double* raw = dev_alloc<double>((size_t)(S * B));   // [S][b], as uploaded
+  double* xt = dev_alloc<double>((size_t)(S * B));    // [b][S]
+  double* wd = dev_alloc<double>((size_t)(2 * S));    // w_lo, w_hi
+  double* res = dev_alloc<double>((size_t)(PS_COLS * B));
+  hipError_t e = raw && xt && wd && res ? hipSuccess : hipErrorOutOfMemory;
+  if (e == hipSuccess) e = hipMemcpy(wd, w_lo, (size_t)S * sizeof(double), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(wd + S, w_hi, (size_t)S * sizeof(double), hipMemcpyHostToDevice);
+  for (int64_t p0 = 0; p0 < P && e == hipSuccess; p0 += B) {
+    const int64_t b = std::min(B, P - p0);
+    e = hipMemcpy2D(raw, (size_t)b * sizeof(double), x + p0, (size_t)P * sizeof(double), (size_t)b * sizeof(double), (size_t)S, hipMemcpyHostToDevice);
+    if (e != hipSuccess) break;
+    hipLaunchKernelGGL(k_summary_transpose, dim3((unsigned)((b + SUM_TILE - 1) / SUM_TILE), (unsigned)((S + SUM_TILE - 1) / SUM_TILE)), dim3(SUM_BLOCK), 0, 0,
+                       (const double*)raw, S, b, xt);
+    hipLaunchKernelGGL(k_psens, dim3((unsigned)b), dim3(PS_BLOCK), 0, 0, (const double*)xt, (int)S, (const double*)wd, (const double*)(wd + S), delta, res, b);
+    e = hipGetLastError();   // (a launch the runtime refuses -- k_psens's LDS -- is reported here, not as a fault)
+    if (e == hipSuccess) e = hipStreamSynchronize(0);
+    if (e == hipSuccess)
+      e = hipMemcpy2D(out + p0, (size_t)P * sizeof(double), res, (size_t)b * sizeof(double), (size_t)b * sizeof(double), PS_COLS, hipMemcpyDeviceToHost);
+  }
+  if (raw) hipFree(raw);
+  if (xt) hipFree(xt);
+  if (wd) hipFree(wd);
+  if (res) hipFree(res);
+  HIPCHK_RET(e, "nuts_psens", NUTS_E_HIP);
   return NUTS_OK;
 }
 

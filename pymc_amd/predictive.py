@@ -252,6 +252,18 @@ def _operands(f, first_arg: int = 0):
         yield from (ins.x, ins.y, ins.z)
 
 
+def bare_prior_factors(spec) -> Dict[int, list]:
+    """variable -> the factors that are its prior by form: not observed, their value the bare variable, of the variable's size
+    (whatever the family: `_prior_analysis` then asks for one it can draw from, `sensitivity` only for a density)."""
+    bare: Dict[int, list] = {}
+    for fi, f in enumerate(spec.factors):
+        t = f.args[0] if f.args else None
+        if t is not None and not getattr(f, "observed", False) and t.a.kind == ms.OP_VAR and t.b == ms.ZERO and t.c == ms.ZERO:
+            if f.size == spec.vars[t.a.ref].size:
+                bare.setdefault(t.a.ref, []).append(fi)
+    return bare
+
+
 def _prior_analysis(spec):
     """-> (why, levels): the reason the prior of `spec` cannot be drawn from (then levels is None), or None and the ancestral order."""
     who = lambda k: f"variable {k} ({spec.vars[k].name!r})"   # noqa: E731
@@ -270,15 +282,11 @@ def _prior_analysis(spec):
             if o.kind == ms.OP_LIN:
                 return f"Potential factor {fi} ({f.name!r}) reads a linear predictor: it reweights the prior", None
     prior_of = {}
-    bare: Dict[int, list] = {}       # variable -> the non-observed factors over the bare variable
-    for fi, f in enumerate(spec.factors):
-        t = f.args[0] if f.args else None
-        if t is not None and not getattr(f, "observed", False) and t.a.kind == ms.OP_VAR and t.b == ms.ZERO and t.c == ms.ZERO:
-            bare.setdefault(t.a.ref, []).append(fi)
+    bare = bare_prior_factors(spec)
     for k, v in enumerate(spec.vars):
         if k > PRIOR_INDEX_MAX:
             return f"{who(k)}: its index does not fit the 14 bits the counter gives it", None
-        over = [fi for fi in bare.get(k, ()) if spec.factors[fi].size == v.size]
+        over = bare.get(k, [])
         found = [fi for fi in over if spec.factors[fi].dist not in REFUSED_FAMILIES + PRIOR_DISCRETE]
         if not over and mix is not None and mix.w_alpha is not None and mix.w_logits == k and getattr(v, "simplex", False):
             prior_of[k] = -1        # the mixture node's Dirichlet weights: the node owns the prior

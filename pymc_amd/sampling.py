@@ -550,6 +550,7 @@ def sample(
     summary: bool = False,
     loo_pit: bool = False,
     prior_predictive=False,
+    psens: bool = False,
     **step_kwargs,
 ):
     """Reduced `pm.sample` (mcmc.py:620-1190) returning raw arrays (and, with ``return_multitrace=True``, the reference's
@@ -606,6 +607,11 @@ def sample(
     *shape)} drawn from the priors in ancestral order on the device and ``result["prior_predictive"]`` = {observed variable: (1, S,
     size)}, one replicate at each of them (`pymc_amd.predictive.sample_prior_predictive`, under the key of
     ``posterior_predictive``).  A model whose prior cannot be drawn from is refused before sampling.
+
+    ``psens`` (`az.psens` for both components, the `priorsense` table): ``result["psens"]`` = the dict of
+    `pymc_amd.sensitivity.psens_table` -- per element of every variable the power-scaling sensitivity to the prior and to the
+    likelihood and the diagnosis -- from the draws the result holds after the gather; a rank left with no draws gets none.  More
+    than 8192 chains x draws are refused before sampling.
     """
     rank, world, local = _dist_info()
     from pymc_amd.lowering import as_model_spec
@@ -635,6 +641,13 @@ def sample(
         why = prior_refusal(spec)
         if why:
             raise ValueError("prior_predictive=True refused: " + why)
+    if psens:
+        from pymc_amd.sensitivity import max_draws as psens_max_draws
+
+        kept = int(draws) + (0 if discard_tuned_samples else int(tune))
+        if int(chains) * kept > psens_max_draws():
+            raise ValueError(f"psens=True refused: {chains} chains x {kept} draws = {int(chains) * kept} draws per parameter exceed the limit of "
+                             f"{psens_max_draws()} (one workgroup sorts a parameter's draws in LDS); a larger trace is out of scope")
     if device is None and world > 1:
         device = local
     # mcmc.py:907-908 -- every rank derives ALL chain generators so chain c is the same stream on any layout
@@ -913,6 +926,11 @@ def sample(
         from pymc_amd.summary import summary as summarize_trace
 
         result["summary"] = summarize_trace(spec, result["draws"], device=device)
+    if psens and result["draws"] is not None and np.shape(result["draws"])[0] > 0:
+        from pymc_amd.sensitivity import psens_table
+
+        f = getattr(step, "_logp_dlogp_func", None)
+        result["psens"] = psens_table(spec, result["draws"], device=device, func=f if hasattr(f, "logdens_sum") else None)
     return result
 
 

@@ -244,6 +244,16 @@ class DeviceValueGradFunction:
         _lib.check(lib.nuts_model_loglik(self._handle, kind, index, _lib.dptr(q), q.shape[0], _lib.dptr(out)), "nuts_model_loglik")
         return out
 
+    def logdens_sum(self, q, node) -> np.ndarray:
+        """The total of node (kind, index)'s pointwise values at each raveled unconstrained draw q [S, n] -> [S], reduced on the device
+        (`nuts_model_logdens_sum`): what `log_likelihood(...).sum(axis=1)` would give, without the [S, size] matrix."""
+        lib = _lib.load()
+        kind, index = int(node[0]), int(node[1])
+        q = np.ascontiguousarray(np.asarray(q, dtype="float64").reshape(-1, self.n))
+        out = np.empty(q.shape[0])
+        _lib.check(lib.nuts_model_logdens_sum(self._handle, kind, index, _lib.dptr(q), q.shape[0], _lib.dptr(out)), "nuts_model_logdens_sum")
+        return out
+
     def waic_accumulator(self, name: str, node=None) -> "WaicAccumulator":
         """Device-resident per-observation WAIC accumulators of observed variable `name` (`nuts_waic_*`)."""
         kind, index = self._ll_node(name, node)
