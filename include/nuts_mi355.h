@@ -403,6 +403,32 @@ int nuts_ppc_update(nuts_ppc *p, const double *q, int64_t S);
 int nuts_ppc_read(nuts_ppc *p, double *mean_i, double *var_i, double *n_lt_i, double *n_eq_i, int64_t *n_draws);
 int nuts_ppc_read_stats(nuts_ppc *p, double *T /* [n_draws][4] */, double *T_obs /* [4] */);
 void nuts_ppc_destroy(nuts_ppc *p);
+/* Predictions at new data (`pm.set_data` + `pm.sample_posterior_predictive(..., predictions=True)`, and the held-out log predictive
+ * density K-fold / train-test validation rest on).  The model is one created from a spec whose observed node carries the NEW rows
+ * (pymc_amd/model_spec.py `with_data`: same free variables, so a draw of the fitted model is a draw of this one).  Per (draw s,
+ * observation i) the engine forms the conditional mean m and variance v of the node's family in closed form (pymc_amd/csrc/predict.h:
+ * every family nuts_model_predictive draws from, and BINOMIAL; TRUNCNORMAL, POTENTIAL and DERIVED are refused) and, with held-out
+ * values, lp = log p(y_i | theta_s), the value nuts_model_loglik gives.  A moment that diverges is +inf, one that does not exist is
+ * NaN, invalid parameters give NaN for both; a draw at which a parameter check of a factor failed has NaN moments and lp = -inf over
+ * the factor's whole row.  Sizes and the order of observations are those of nuts_model_loglik_size / nuts_model_loglik.
+ *   nuts_model_predict_moments: q host [S][ndim] raveled UNCONSTRAINED draws; mean host [S][N]; var NULL or host [S][N]
+ * Streaming fold: per observation Welford's (mean, M2) of m over the draws, the running mean of v, the running log-sum-exp of lp and
+ * the count, on the device, batch by batch; no [S][N] matrix exists anywhere.  The state after draws fed in any split is bitwise that
+ * after one call.  NaN is not hidden: an observation that met a NaN moment stays NaN.  lp = -inf carries weight 0; an observation
+ * whose every lp is -inf has lpd = -inf.
+ *   nuts_pred_create: with_y != 0: the node's observed values are held-out values (lp is folded); 0: they are placeholders
+ *   nuts_pred_read:   mean_i, var_between_i = M2 / S, var_within_i = mean of v, lpd_i = log mean_s exp(lp) (NUTS_E_ARG on a handle
+ *                     created without held-out values); any of them may be NULL
+ * The law of total variance gives the predictive variance of the empirical mixture of the draws: var_between_i + var_within_i.
+ * The batch size is option NUTS_LL_B, as for the log-likelihood.  Destroy the handle before its model. */
+int nuts_model_predict_moments(nuts_model *m, int32_t kind, int32_t index, const double *q, int64_t S, double *mean /* host [S][N] */,
+                               double *var /* NULL or host [S][N] */);
+typedef struct nuts_pred nuts_pred;
+nuts_pred *nuts_pred_create(nuts_model *m, int32_t kind, int32_t index, int32_t with_y);
+int nuts_pred_update(nuts_pred *p, const double *q, int64_t S);
+int nuts_pred_read(nuts_pred *p, double *mean_i, double *var_between_i, double *var_within_i, double *lpd_i /* NULL without y */,
+                   int64_t *n_draws);
+void nuts_pred_destroy(nuts_pred *p);
 /* Prior draws (`pm.sample_prior_predictive`, its first half): S positions drawn from the PRIORS of the free variables, in ancestral
  * order, on the device (pymc_amd/csrc/prior.h, prior_kernel.h).  A free variable has a samplable prior when exactly one factor has
  * the bare variable as its argument 0, the variable's size, and a continuous family nuts_model_predictive draws from; the factor's

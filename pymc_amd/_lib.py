@@ -302,6 +302,11 @@ SYMBOLS = {
     "nuts_ppc_read": (C.c_int, [_VP, _PD, _PD, _PD, _PD, C.POINTER(C.c_int64)]),
     "nuts_ppc_read_stats": (C.c_int, [_VP, _PD, _PD]),
     "nuts_ppc_destroy": (None, [_VP]),
+    "nuts_model_predict_moments": (C.c_int, [_VP, C.c_int32, C.c_int32, _PD, C.c_int64, _PD, _PD]),
+    "nuts_pred_create": (_VP, [_VP, C.c_int32, C.c_int32, C.c_int32]),
+    "nuts_pred_update": (C.c_int, [_VP, _PD, C.c_int64]),
+    "nuts_pred_read": (C.c_int, [_VP, _PD, _PD, _PD, _PD, C.POINTER(C.c_int64)]),
+    "nuts_pred_destroy": (None, [_VP]),
     "nuts_loo_pit_create": (_VP, [_VP, C.c_uint64]),
     "nuts_loo_pit_update": (C.c_int, [_VP, _PD, C.c_int64, C.c_int64]),
     "nuts_loo_pit_read": (C.c_int, [_VP, _PD, _PD, _PD, _PD, _PD, _PD, C.POINTER(C.c_int64)]),

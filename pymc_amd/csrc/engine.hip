@@ -26,6 +26,7 @@
 #include "mixture_kernel.h"
 #include "loglik_kernel.h"
 #include "predictive_kernel.h"
+#include "predict_kernel.h"
 #include "prior_kernel.h"
 #include "loo_pit_kernel.h"
 #include "summary_kernel.h"
@@ -2653,8 +2654,8 @@ static int pp_draw_range(int64_t draw0, int64_t S) {
 }
 
 // y_rep of draws q[0 .. nb) (host, [nb][n]), numbered s0 .. s0 + nb - 1, into m->ll_stage [nb][N]; stream-ordered, no synchronisation.
-// The routes are those of ll_eval_batch.
-static int pp_eval_batch(nuts_model* m, int kind, int index, const double* q, int nb, int64_t N, int B, PPAddr ad) {
+// The routes are those of ll_eval_batch.  variates = false (GLM node and logit rows only) leaves the linear predictor in the stage.
+static int pp_eval_batch(nuts_model* m, int kind, int index, const double* q, int nb, int64_t N, int B, PPAddr ad, bool variates = true) {
   const ModelDev& md = m->md;
   const int n = md.n;
   HIPCHK(hipMemcpyAsync(m->ll_q, q, (size_t)nb * n * sizeof(double), hipMemcpyHostToDevice, m->stream));
@@ -2706,14 +2707,14 @@ static int pp_eval_batch(nuts_model* m, int kind, int index, const double* q, in
     }
 #undef PPG
     const int dist = gm.family == NUTS_GLM_NORMAL ? NUTS_D_NORMAL : (gm.family == NUTS_GLM_BERNOULLI ? NUTS_D_BERNOULLI_LOGIT : NUTS_D_POISSON);
-    hipLaunchKernelGGL(k_pp_draw, dim3(nblk, nb), dim3(LL_BLOCK), 0, m->stream, m->ll_stage, N, dist, (const double*)m->ll_sc, ad);
+    if (variates) hipLaunchKernelGGL(k_pp_draw, dim3(nblk, nb), dim3(LL_BLOCK), 0, m->stream, m->ll_stage, N, dist, (const double*)m->ll_sc, ad);
   } else if (kind == NUTS_LL_LOGIT_ROWS) {
     const RowsDev& lg = md.lg;
     const int64_t GD = (int64_t)lg.G * lg.D;
     hipLaunchKernelGGL(k_ll_rows_beta, dim3((unsigned)((GD + LL_BLOCK - 1) / LL_BLOCK), nb), dim3(LL_BLOCK), 0, m->stream, md, (const double*)m->ll_q, m->ll_par);
     hipLaunchKernelGGL(k_pp_rows, dim3(nblk, nb), dim3(LL_BLOCK), 0, m->stream, md, (const double*)m->ll_par, WAVE * m->rows_rpl,
                        lg.ga_gpw ? 1 : lg.ga_w, m->ll_stage);
-    hipLaunchKernelGGL(k_pp_draw, dim3(nblk, nb), dim3(LL_BLOCK), 0, m->stream, m->ll_stage, N, (int)NUTS_D_BERNOULLI_LOGIT, (const double*)m->ll_sc, ad);
+    if (variates) hipLaunchKernelGGL(k_pp_draw, dim3(nblk, nb), dim3(LL_BLOCK), 0, m->stream, m->ll_stage, N, (int)NUTS_D_BERNOULLI_LOGIT, (const double*)m->ll_sc, ad);
   } else
     hipLaunchKernelGGL(k_pp_mix, dim3(nblk, nb), dim3(MIX_BLOCK), 0, m->stream, md, (const double*)m->ll_q, m->ll_stage, ad);
   HIPCHK(hipGetLastError());
@@ -3013,6 +3014,219 @@ extern "C" void nuts_ppc_destroy(nuts_ppc* p) {
   hipStreamSynchronize(p->m->stream);
   p->m->n_waic--;
   ppc_free(p);
+}
+
+// ---- predictions at new data: conditional moments and their streaming fold (predict.h, predict_kernel.h) ----------------------------
+// The model is one built from `with_data(spec, new)` (pymc_amd/model_spec.py): the node's rows are the new rows.  What
+// nuts_model_loglik accepts, less the families predict.h has no moments for.
+static int pd_check(nuts_model* m, int kind, int index, int64_t* N) {
+  if (const int rc = ll_check(m, kind, index, N)) return rc;
+  if (kind == NUTS_LL_FACTOR) {
+    const int dist = m->fac_host[index].dist;
+    if (!pd_family_ok(dist)) {
+      g_err = std::string("predictions: ") + prior_family_name(dist) + " is out of scope (no conditional moments for it)";
+      return NUTS_E_ARG;
+    }
+  }
+  return NUTS_OK;
+}
+
+static int pd_family(const ModelDev& md, int kind) { return kind == NUTS_LL_GLM ? md.glm.family : NUTS_GLM_BERNOULLI; }
+
+// per-draw preparation of a factor that reads a predictor column or a derived vector (as ll_eval_batch)
+static void pd_factor_position(nuts_model* m, const ArenaDev& A, EvalIO& io, int b) {
+  const ModelDev& md = m->md;
+  io.q = m->ll_q + (size_t)b * md.n;
+  if (md.n_derived > 0 && md.n_lins == 0) hipLaunchKernelGGL(k_derive, dim3(2), dim3(256), 0, m->stream, md, A, io, 0);
+  launch_lin_forward(m, A, io, 0);
+}
+
+// conditional means of draws q[0 .. nb) (host, [nb][n]) into m->ll_stage [nb][N], variances into var [nb][N] (device; nullptr: not
+// wanted); stream-ordered, no synchronisation
+static int pd_moments_batch(nuts_model* m, int kind, int index, const double* q, int nb, int64_t N, int B, double* var) {
+  const ModelDev& md = m->md;
+  const int n = md.n;
+  if (kind == NUTS_LL_GLM || kind == NUTS_LL_LOGIT_ROWS) {
+    if (const int rc = pp_eval_batch(m, kind, index, q, nb, N, B, PPAddr{}, false)) return rc;
+    if (N == 0) return NUTS_OK;
+    hipLaunchKernelGGL(k_pd_moments_eta, dim3((unsigned)((N + LL_BLOCK - 1) / LL_BLOCK), nb), dim3(LL_BLOCK), 0, m->stream, m->ll_stage, N,
+                       pd_family(md, kind), (const double*)m->ll_sc, var);
+    HIPCHK(hipGetLastError());
+    return NUTS_OK;
+  }
+  HIPCHK(hipMemcpyAsync(m->ll_q, q, (size_t)nb * n * sizeof(double), hipMemcpyHostToDevice, m->stream));
+  if (N == 0) return NUTS_OK;
+  const unsigned nblk = (unsigned)((N + LL_BLOCK - 1) / LL_BLOCK);
+  if (kind == NUTS_LL_FACTOR) {
+    HIPCHK(hipMemsetAsync(m->ll_dead, 0, LL_B * sizeof(int32_t), m->stream));
+    if (md.n_lins > 0 || md.n_derived > 0) {
+      ArenaDev A{};
+      A.n = n; A.nblk = md.nblk; A.ept = m->ept; A.S = 1;
+      EvalIO io{};
+      io.mode = MODE_PLAIN; io.lean = md.lean_ok;
+      for (int b = 0; b < nb; ++b) {
+        pd_factor_position(m, A, io, b);
+        hipLaunchKernelGGL(k_pd_moments_factor, dim3(nblk, 1), dim3(LL_BLOCK), 0, m->stream, md, io.q, index, m->ll_stage + (size_t)b * N,
+                           var ? var + (size_t)b * N : nullptr, m->ll_dead + b);
+      }
+    } else
+      hipLaunchKernelGGL(k_pd_moments_factor, dim3(nblk, nb), dim3(LL_BLOCK), 0, m->stream, md, (const double*)m->ll_q, index, m->ll_stage, var, m->ll_dead);
+    hipLaunchKernelGGL(k_pp_fill, dim3(nblk, nb), dim3(LL_BLOCK), 0, m->stream, m->ll_stage, N, (const int32_t*)m->ll_dead);
+    if (var) hipLaunchKernelGGL(k_pp_fill, dim3(nblk, nb), dim3(LL_BLOCK), 0, m->stream, var, N, (const int32_t*)m->ll_dead);
+  } else
+    hipLaunchKernelGGL(k_pd_moments_mix, dim3(nblk, nb), dim3(MIX_BLOCK), 0, m->stream, md, (const double*)m->ll_q, m->ll_stage, var);
+  HIPCHK(hipGetLastError());
+  return NUTS_OK;
+}
+
+extern "C" int nuts_model_predict_moments(nuts_model* m, int32_t kind, int32_t index, const double* q, int64_t S, double* mean, double* var) {
+  int64_t N = 0;
+  if (const int rc = pd_check(m, kind, index, &N)) return rc;
+  if (S < 0 || (S > 0 && (!q || !mean))) { g_err = "null argument"; return NUTS_E_ARG; }
+  if (const int rc = ll_ensure(m, kind, N)) return rc;
+  double* var_dev = nullptr;
+  if (var && S > 0 && hipMalloc((void**)&var_dev, (size_t)LL_B * std::max<int64_t>(N, 1) * sizeof(double)) != hipSuccess) {
+    (void)hipGetLastError();
+    g_err = "predictions: device allocation failed";
+    return NUTS_E_HIP;
+  }
+  const int B = ll_batch();
+  int rc = NUTS_OK;
+  hipError_t he = hipSuccess;
+  for (int64_t s0 = 0; s0 < S && rc == NUTS_OK && he == hipSuccess; s0 += B) {
+    const int nb = (int)std::min<int64_t>(B, S - s0);
+    rc = pd_moments_batch(m, kind, index, q + (size_t)s0 * m->md.n, nb, N, B, var_dev);
+    if (rc != NUTS_OK) break;
+    he = hipMemcpyAsync(mean + (size_t)s0 * N, m->ll_stage, (size_t)nb * N * sizeof(double), hipMemcpyDeviceToHost, m->stream);
+    if (he == hipSuccess && var_dev) he = hipMemcpyAsync(var + (size_t)s0 * N, var_dev, (size_t)nb * N * sizeof(double), hipMemcpyDeviceToHost, m->stream);
+    if (he == hipSuccess) he = hipStreamSynchronize(m->stream);
+  }
+  if (var_dev) hipFree(var_dev);
+  if (rc != NUTS_OK) return rc;
+  HIPCHK(he);
+  HIPCHK(hipGetLastError());
+  return NUTS_OK;
+}
+
+struct nuts_pred {
+  nuts_model* m;
+  int32_t kind, index, with_y;
+  int64_t N, count;
+  const double* y;        // [N] held-out values in the node's evaluation order (GLM node, logit rows), nullptr without them
+  double *y_own, *acc;    // acc [PD_ACC_ROWS][N]: the rows of PDAcc (predict.h)
+};
+
+static void pred_free(nuts_pred* p) {
+  for (double* d : {p->y_own, p->acc}) if (d) hipFree(d);
+  delete p;
+}
+
+extern "C" nuts_pred* nuts_pred_create(nuts_model* m, int32_t kind, int32_t index, int32_t with_y) {
+  int64_t N = 0;
+  if (pd_check(m, kind, index, &N)) return nullptr;
+  if (ll_ensure(m, kind, N)) return nullptr;
+  auto* p = new nuts_pred{m, kind, index, with_y ? 1 : 0, N, 0, nullptr, nullptr, nullptr};
+  const size_t n1 = (size_t)std::max<int64_t>(N, 1);
+  const bool own = p->with_y && kind == NUTS_LL_LOGIT_ROWS;
+  if ((own && hipMalloc((void**)&p->y_own, n1 * sizeof(double)) != hipSuccess) || hipMalloc((void**)&p->acc, PD_ACC_ROWS * n1 * sizeof(double)) != hipSuccess) {
+    (void)hipGetLastError();
+    g_err = "predictions: device allocation failed";
+    pred_free(p);
+    return nullptr;
+  }
+  if (N > 0) {
+    if (p->with_y && (kind == NUTS_LL_GLM || kind == NUTS_LL_LOGIT_ROWS)) p->y = pp_y_obs(m, kind, index, N, p->y_own);
+    hipLaunchKernelGGL(k_pd_init, dim3((unsigned)((N + LL_BLOCK - 1) / LL_BLOCK)), dim3(LL_BLOCK), 0, m->stream, N, p->acc);
+  }
+  if (hipStreamSynchronize(m->stream) != hipSuccess || hipGetLastError() != hipSuccess) {
+    g_err = "predictions: building the accumulators failed";
+    pred_free(p);
+    return nullptr;
+  }
+  m->n_waic++;
+  return p;
+}
+
+extern "C" int nuts_pred_update(nuts_pred* p, const double* q, int64_t S) {
+  if (!p || S < 0 || (S > 0 && !q)) { g_err = "null argument"; return NUTS_E_ARG; }
+  nuts_model* m = p->m;
+  const ModelDev& md = m->md;
+  const int kind = p->kind, index = p->index, n = md.n;
+  int64_t N = 0;
+  if (const int rc = pd_check(m, kind, index, &N)) return rc;
+  if (const int rc = ll_ensure(m, kind, N)) return rc;
+  const int B = ll_batch();
+  const unsigned nblk = (unsigned)((N + LL_BLOCK - 1) / LL_BLOCK);
+  for (int64_t s0 = 0; s0 < S; s0 += B) {
+    const int nb = (int)std::min<int64_t>(B, S - s0);
+    const double* qb = q + (size_t)s0 * n;
+    if (kind == NUTS_LL_GLM || kind == NUTS_LL_LOGIT_ROWS) {
+      if (const int rc = pp_eval_batch(m, kind, index, qb, nb, N, B, PPAddr{}, false)) return rc;
+      if (N > 0) {
+        const int family = pd_family(md, kind);
+        const double* lfact = p->y && kind == NUTS_LL_GLM && family == NUTS_GLM_POISSON ? m->ll_lfact : nullptr;
+        hipLaunchKernelGGL(k_pd_fold_eta, dim3(nblk), dim3(LL_BLOCK), 0, m->stream, (const double*)m->ll_stage, nb, N, family, (const double*)m->ll_sc,
+                           p->y, lfact, p->acc);
+      }
+    } else {
+      HIPCHK(hipMemcpyAsync(m->ll_q, qb, (size_t)nb * n * sizeof(double), hipMemcpyHostToDevice, m->stream));
+      if (N > 0 && kind == NUTS_LL_FACTOR) {
+        HIPCHK(hipMemsetAsync(m->ll_dead, 0, LL_B * sizeof(int32_t), m->stream));
+        if (md.n_lins > 0 || md.n_derived > 0) {
+          ArenaDev A{};
+          A.n = n; A.nblk = md.nblk; A.ept = m->ept; A.S = 1;
+          EvalIO io{};
+          io.mode = MODE_PLAIN; io.lean = md.lean_ok;
+          for (int b = 0; b < nb; ++b) {
+            pd_factor_position(m, A, io, b);
+            hipLaunchKernelGGL(k_pd_flags, dim3(nblk, 1), dim3(LL_BLOCK), 0, m->stream, md, io.q, index, m->ll_dead + b);
+            hipLaunchKernelGGL(k_pd_fold_factor, dim3(nblk), dim3(LL_BLOCK), 0, m->stream, md, io.q, index, 1, (const int32_t*)(m->ll_dead + b), p->with_y, p->acc);
+          }
+        } else {
+          hipLaunchKernelGGL(k_pd_flags, dim3(nblk, nb), dim3(LL_BLOCK), 0, m->stream, md, (const double*)m->ll_q, index, m->ll_dead);
+          hipLaunchKernelGGL(k_pd_fold_factor, dim3(nblk), dim3(LL_BLOCK), 0, m->stream, md, (const double*)m->ll_q, index, nb, (const int32_t*)m->ll_dead,
+                             p->with_y, p->acc);
+        }
+      } else if (N > 0) {
+        const dim3 grid(nblk), block(MIX_BLOCK);
+        if (md.mix.K <= 4) hipLaunchKernelGGL(k_pd_fold_mix<4>, grid, block, 0, m->stream, md, (const double*)m->ll_q, nb, p->with_y, p->acc);
+        else if (md.mix.K <= 8) hipLaunchKernelGGL(k_pd_fold_mix<8>, grid, block, 0, m->stream, md, (const double*)m->ll_q, nb, p->with_y, p->acc);
+        else hipLaunchKernelGGL(k_pd_fold_mix<16>, grid, block, 0, m->stream, md, (const double*)m->ll_q, nb, p->with_y, p->acc);
+      }
+    }
+    p->count += nb;
+  }
+  HIPCHK(hipStreamSynchronize(m->stream));   // (the caller may reuse q)
+  HIPCHK(hipGetLastError());
+  return NUTS_OK;
+}
+
+extern "C" int nuts_pred_read(nuts_pred* p, double* mean_i, double* var_between_i, double* var_within_i, double* lpd_i, int64_t* n_draws) {
+  if (!p) { g_err = "null argument"; return NUTS_E_ARG; }
+  if (n_draws) *n_draws = p->count;
+  if (lpd_i && !p->with_y) { g_err = "predictions: the accumulators were created without held-out values (no lpd)"; return NUTS_E_ARG; }
+  const int64_t N = p->N;
+  if (N == 0 || (!mean_i && !var_between_i && !var_within_i && !lpd_i)) return NUTS_OK;
+  HIPCHK(hipStreamSynchronize(p->m->stream));
+  double* dst[3] = {mean_i, var_between_i, var_within_i};
+  for (int k = 0; k < 3; ++k)
+    if (dst[k]) HIPCHK(hipMemcpy(dst[k], p->acc + (size_t)k * N, (size_t)N * sizeof(double), hipMemcpyDeviceToHost));
+  const double S = (double)p->count;
+  if (var_between_i)   // M2 / S, the population variance
+    for (int64_t i = 0; i < N; ++i) var_between_i[i] /= S;
+  if (lpd_i) {
+    std::vector<double> lr(2 * (size_t)N);
+    HIPCHK(hipMemcpy(lr.data(), p->acc + 3 * (size_t)N, 2 * (size_t)N * sizeof(double), hipMemcpyDeviceToHost));
+    for (int64_t i = 0; i < N; ++i) lpd_i[i] = std::log(lr[N + i]) + lr[i] - std::log(S);
+  }
+  return NUTS_OK;
+}
+
+extern "C" void nuts_pred_destroy(nuts_pred* p) {
+  if (!p) return;
+  hipStreamSynchronize(p->m->stream);
+  p->m->n_waic--;
+  pred_free(p);
 }
 
 // ---- LOO predictive checks: the second pass (psis.h psis_fit / psis_weight, loo_pit_kernel.h) ----------------------

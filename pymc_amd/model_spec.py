@@ -302,6 +302,8 @@ class ModelSpec:
     # logit rows: `rows_order[i]` = the caller's index of row i of `logit_rows` when the rows had to be sorted by group (None: they
     # were passed sorted).  Pointwise results of the node are returned in the caller's order.
     rows_order: Optional[np.ndarray] = None
+    # `with_data`: the observed variables whose observed values are placeholders (new rows without held-out values)
+    predict_no_y: Tuple[str, ...] = ()
 
     @property
     def n(self) -> int:
@@ -1023,3 +1025,265 @@ class ModelBuilder:
 
     def build(self) -> ModelSpec:
         return self.spec
+
+
+# ---------------------------------------------------------------------------
+# New data under a fitted model (`pm.set_data`)
+# ---------------------------------------------------------------------------
+# `with_data(spec, new)` is the spec of the SAME model at other rows: the free variables, their offsets and transforms, the factors'
+# terms and programs are those of `spec` (a trace of the fitted model is a trace of the result); only the data of the named observed
+# nodes is replaced.  `pymc_amd.predictive.predict` evaluates it (include/nuts_mi355.h, "Predictions at new data").
+
+
+def _factor_operands(f: Factor):
+    """Every operand the factor reads, in the order its arguments first read them (an argument's OP_TMP is followed into the
+    program, depth first), each instruction once."""
+    prog = tuple(getattr(f, "prog", ()) or ())
+    seen = set()
+
+    def walk(o: Operand):
+        if o.kind == OP_TMP:
+            if o.ref in seen or not 0 <= o.ref < len(prog):
+                return
+            seen.add(o.ref)
+            ins = prog[o.ref]
+            for x in (ins.x, ins.y, ins.z):
+                yield from walk(x)
+        else:
+            yield o
+
+    for t in f.args:
+        for o in (t.a, t.b, t.c):
+            yield from walk(o)
+
+
+def _data_ids(f: Factor) -> List[int]:
+    """Data ids a factor reads (plain vectors and the index vectors of its gathers), in first-read order, without repeats."""
+    out: List[int] = []
+    for o in _factor_operands(f):
+        did = o.ref if o.kind == OP_DATA else (int(o.c) if o.kind == OP_GATHER else None)
+        if did is not None and did not in out:
+            out.append(did)
+    return out
+
+
+def _convention_arg(f: Factor) -> Optional[int]:
+    """The argument the builder computes from the observed values: Poisson's second (`gammaln(y + 1)`), Binomial's third (the log
+    binomial coefficient of (n, y))."""
+    return {D_POISSON: 2, D_BINOMIAL: 3}.get(f.dist)
+
+
+def _factor_inputs(f: Factor) -> Tuple[Optional[int], Optional[int], List[int]]:
+    """-> (data id of the observed values or None, data id of the convention argument or None, the other data ids)."""
+    v = f.args[0]
+    obs = v.a.ref if v.a.kind == OP_DATA and (v.b == ZERO or v.c == ZERO) else None
+    ca = _convention_arg(f)
+    conv = None
+    if ca is not None and ca < len(f.args) and f.args[ca].a.kind == OP_DATA:
+        conv = f.args[ca].a.ref
+    return obs, conv, [d for d in _data_ids(f) if d != obs and d != conv]
+
+
+def data_inputs(spec: "ModelSpec") -> Dict[str, dict]:
+    """What `with_data` expects per observed variable: the keys of its dict.  Logit rows: {"X": D, "group_idx": G, "y": None};
+    GLM node: {"X": P, "y": None}; marginal mixture: {"y": None}; an observed factor: {"data": [data ids, in the order its
+    arguments first read them], "observed": None}.  The numbers are the dimensions the fitted model fixes; None marks what is
+    optional (held-out values)."""
+    out: Dict[str, dict] = {}
+    for name, kind, index, _ in observed_nodes(spec):
+        if kind == LL_LOGIT_ROWS:
+            r = spec.logit_rows
+            D = spec.vars[r.mu].size
+            out[name] = {"X": D, "group_idx": spec.vars[r.z].size // D, "y": None}
+        elif kind == LL_GLM:
+            out[name] = {"X": int(spec.glm_rows.X.shape[1]), "y": None}
+        elif kind == LL_MIXTURE:
+            out[name] = {"y": None}
+        else:
+            out[name] = {"data": _factor_inputs(spec.factors[index])[2], "observed": None}
+    return out
+
+
+def _vector(x, what: str, name: str) -> np.ndarray:
+    a = np.ascontiguousarray(np.asarray(x, dtype="float64"))
+    if a.ndim > 1:
+        raise ValueError(f"with_data: {name!r}: {what} must be a vector, got shape {a.shape}")
+    return np.ascontiguousarray(a.ravel())
+
+
+def _with_factor_data(out: "ModelSpec", fi: int, d: dict) -> bool:
+    from scipy.special import gammaln
+
+    f = out.factors[fi]
+    name = f.name
+    unknown = set(d) - {"data", "observed"}
+    if unknown:
+        raise ValueError(f"with_data: {name!r} is an observed factor: its dict holds 'data' and 'observed', not {sorted(unknown)}")
+    if any(o.kind == OP_LIN for o in _factor_operands(f)):
+        raise ValueError(f"with_data: {name!r} reads a linear-predictor matrix (lins): new data under it is out of scope")
+    obs_id, conv_id, ids = _factor_inputs(f)
+    if obs_id is None:
+        raise ValueError(f"with_data: {name!r}: the factor's value is an expression of variables, not observed data")
+    given = {int(k): _vector(v, f"data vector {int(k)}", name) for k, v in (d.get("data") or {}).items()}
+    extra_ids = sorted(set(given) - set(ids))
+    if extra_ids:
+        raise ValueError(f"with_data: {name!r} does not read data vectors {extra_ids} (it reads {ids}; `data_inputs` lists them)")
+    # a vector another factor or a Deterministic also reads cannot change under this one alone
+    mine = set(ids) | {obs_id} | ({conv_id} if conv_id is not None else set())
+    for gi, g in enumerate(out.factors):
+        shared = sorted(mine & set(_data_ids(g))) if gi != fi else []
+        if shared:
+            raise ValueError(f"with_data: {name!r}: data vector {shared[0]} is also read by factor {g.name!r}")
+    for dn, (prog, term, _) in out.deterministics.items():
+        shared = sorted(mine & set(_data_ids(Factor(D_POTENTIAL, 1, (term,), prog=tuple(prog)))))
+        if shared:
+            raise ValueError(f"with_data: {name!r}: Deterministic {dn!r} reads data vector {shared[0]} that would be replaced")
+    node_ids = []
+    if out.mixture_rows is not None and out.mixture_rows.assign is not None:
+        node_ids.append(out.mixture_rows.assign)
+    if mine & set(node_ids):
+        raise ValueError(f"with_data: {name!r}: a data vector of the factor is the mixture node's")
+    # the new length: every vector of the factor's own length at one M; a factor of scalars takes it from `observed`
+    own = [k for k in ids if out.data[k].size == f.size and f.size > 1]
+    has_y = d.get("observed") is not None
+    y = _vector(d["observed"], "observed", name) if has_y else None
+    if own:
+        missing = [k for k in own if k not in given]
+        if missing:
+            raise ValueError(f"with_data: {name!r}: data vectors {missing} have the factor's length and must be given too")
+        sizes = {given[k].size for k in own}
+        if len(sizes) != 1:
+            raise ValueError(f"with_data: {name!r}: its data vectors must share one new length, got {sorted(sizes)}")
+        M = sizes.pop()
+    elif has_y:
+        M = y.size
+    else:
+        raise ValueError(f"with_data: {name!r}: its parameters are all scalars and no 'observed' is given: nothing sets the new length")
+    if M < 1:
+        raise ValueError(f"with_data: {name!r}: no new rows")
+    if has_y and y.size != M:
+        raise ValueError(f"with_data: {name!r}: 'observed' has {y.size} elements, the new data {M}")
+    for k, v in given.items():
+        if k not in own and v.size not in (1, M):
+            raise ValueError(f"with_data: {name!r}: data vector {k} has {v.size} elements, the new data {M}")
+    for o in _factor_operands(f):
+        if o.kind == OP_VAR and out.vars[o.ref].size > 1 and out.vars[o.ref].size != M:
+            raise ValueError(f"with_data: {name!r} reads variable {out.vars[o.ref].name!r} element by element: its {out.vars[o.ref].size} "
+                             f"elements fix the length, the new data has {M}")
+        if o.kind == OP_GATHER:
+            idx = given.get(int(o.c), out.data[int(o.c)])
+            if idx.size != M:
+                raise ValueError(f"with_data: {name!r}: index vector {int(o.c)} has {idx.size} elements, the new data {M}")
+            if np.any(idx != np.floor(idx)) or np.any(idx < 0) or np.any(idx >= out.vars[o.ref].size):
+                raise ValueError(f"with_data: {name!r}: index vector {int(o.c)} leaves variable {out.vars[o.ref].name!r}")
+    for k, v in given.items():
+        out.data[k] = v
+    if y is None:
+        y = np.zeros(M)
+    out.data[obs_id] = y
+    args = f.args
+    ca = _convention_arg(f)
+    if ca is not None:
+        if f.dist == D_POISSON:
+            conv = gammaln(y + 1)
+        else:
+            n_op = f.args[1].a
+            nn = np.broadcast_to(out.data[n_op.ref] if n_op.kind == OP_DATA else np.float64(n_op.c), y.shape)
+            conv = gammaln(nn + 1) - gammaln(y + 1) - gammaln(nn - y + 1)
+        if conv_id is not None:
+            out.data[conv_id] = np.ascontiguousarray(conv)
+        elif M == 1:    # a scalar observation: the builder kept the value as a constant of the factor
+            args = tuple(Term(Operand(OP_CONST, float(conv[0]))) if i == ca else t for i, t in enumerate(f.args))
+        else:
+            raise ValueError(f"with_data: {name!r} was fitted to a scalar observation: its constant cannot become a vector")
+    out.factors[fi] = Factor(f.dist, int(M), args, f.konst, f.name, f.prog, observed=True)
+    return has_y
+
+
+def with_data(spec: "ModelSpec", new: Dict[str, dict]) -> "ModelSpec":
+    """The spec of the fitted model `spec` at new data: same free variables (so a trace of `spec` is a trace of the result), same
+    factors and programs, the data of the observed variables named in `new` replaced.  `new[name]` is a dict (see `data_inputs`):
+
+      logit rows        X [M, D], group_idx [M] with values in [0, G), optionally y -- rows in any order (they are sorted by group as
+                        the builder sorts them; pointwise results come back in the caller's order through `loglik.caller_order`)
+      GLM node          X [M, P], optionally y
+      marginal mixture  y
+      observed factor   data: {data id: vector} for the data vectors the factor reads, optionally observed
+
+    Without y / observed a placeholder of zeros stands in and the name is listed in the result's `predict_no_y`.  Refused by name:
+    specs with `extra` inputs and the conditional mixture (`loglik.refusal`'s reasons), linear-predictor matrices that feed an
+    observed factor, data another factor or a Deterministic also reads."""
+    import copy
+
+    if getattr(spec, "extra", None):
+        raise ValueError("with_data: the spec has extra inputs " + repr(sorted(spec.extra)) + ": its likelihood depends on the state "
+                         "another step method held at each draw, which the continuous draws do not carry")
+    nodes = {nd[0]: nd for nd in observed_nodes(spec)}
+    missing = [k for k in new if k not in nodes]
+    if missing:
+        raise KeyError(f"with_data: not observed variables of the model: {missing} (observed: {sorted(nodes)})")
+    out = copy.copy(spec)
+    out.data = list(spec.data)
+    out.factors = list(spec.factors)
+    no_y = [k for k in getattr(spec, "predict_no_y", ()) if k not in new]
+    for name, d in new.items():
+        if not isinstance(d, dict):
+            raise TypeError(f"with_data: {name!r}: a dict of arrays is expected (see data_inputs)")
+        _, kind, index, _ = nodes[name]
+        if kind == LL_LOGIT_ROWS:
+            r = spec.logit_rows
+            D = spec.vars[r.mu].size
+            G = spec.vars[r.z].size // D
+            if "X" not in d or "group_idx" not in d:
+                raise ValueError(f"with_data: {name!r} (logit rows) needs 'X' [M, {D}] and 'group_idx' [M]")
+            X = np.ascontiguousarray(d["X"], dtype="float64")
+            g = np.asarray(d["group_idx"])
+            if X.ndim != 2 or X.shape[1] != D:
+                raise ValueError(f"with_data: {name!r}: X must be [M, {D}] as the fitted model's, got {X.shape}")
+            if g.shape != (X.shape[0],) or X.shape[0] < 1:
+                raise ValueError(f"with_data: {name!r}: one group index per new row (at least one row)")
+            if np.any(g != np.floor(g)) or np.any(g < 0) or np.any(g >= G):
+                raise ValueError(f"with_data: {name!r}: group_idx must stay in [0, {G}): new groups are out of scope")
+            g = np.ascontiguousarray(g, dtype="int32")
+            has_y = d.get("y") is not None
+            y = np.asarray(d["y"]) if has_y else np.zeros(X.shape[0], dtype="int8")
+            if y.shape != g.shape:
+                raise ValueError(f"with_data: {name!r}: y has shape {y.shape}, the new rows {g.shape}")
+            order = None
+            if np.any(np.diff(g) < 0):
+                order = np.argsort(g, kind="stable")
+                X, g, y = X[order], g[order], y[order]
+            out.rows_order = order
+            out.logit_rows = LogitRows(np.ascontiguousarray(X), np.ascontiguousarray(y, dtype="int8"), g, r.mu, r.sigma, r.z, r.name)
+        elif kind == LL_GLM:
+            node = spec.glm_rows
+            P = node.X.shape[1]
+            if "X" not in d:
+                raise ValueError(f"with_data: {name!r} (GLM node) needs 'X' [M, {P}]")
+            X = np.ascontiguousarray(d["X"], dtype="float64")
+            if X.ndim != 2 or X.shape[1] != P or X.shape[0] < 1:
+                raise ValueError(f"with_data: {name!r}: X must be [M, {P}] as the fitted model's, got {X.shape}")
+            has_y = d.get("y") is not None
+            y = np.ascontiguousarray(d["y"], dtype="float64").ravel() if has_y else np.zeros(X.shape[0])
+            if y.size != X.shape[0]:
+                raise ValueError(f"with_data: {name!r}: y has {y.size} elements, X {X.shape[0]} rows")
+            out.glm_rows = copy.copy(node)
+            out.glm_rows.X, out.glm_rows.y = X, y
+        elif kind == LL_MIXTURE:
+            node = spec.mixture_rows
+            if node.assign is not None:
+                raise ValueError(f"with_data: {name!r} is a conditional mixture: its likelihood depends on the assignments another step "
+                                 "method rewrites per draw (only the marginal form is supported)")
+            if d.get("y") is None:
+                raise ValueError(f"with_data: {name!r} (marginal mixture) has no covariates: 'y' is its only data")
+            has_y = True
+            out.mixture_rows = copy.copy(node)
+            out.mixture_rows.y = np.ascontiguousarray(d["y"], dtype="float64").ravel()
+            if out.mixture_rows.y.size < 1:
+                raise ValueError(f"with_data: {name!r}: no new rows")
+        else:
+            has_y = _with_factor_data(out, index, d)
+        if not has_y:
+            no_y.append(name)
+    out.predict_no_y = tuple(no_y)
+    return out

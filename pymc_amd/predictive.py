@@ -234,6 +234,96 @@ def loo_pit(model, draws, *, var_name: Optional[str] = None, reff: float = 1.0, 
     return loo_pit_from_accumulators(*cols, elpd_i, khat, lppd_i, n_draws, pointwise=pointwise)
 
 
+# ---- predictions at new data -----------------------------------------------------------------------------------------------------------
+# `pm.set_data(...)` + `pm.sample_posterior_predictive(..., predictions=True)`: the fitted model at rows it has not seen
+# (`model_spec.with_data`), and the held-out log predictive density K-fold and train/test validation rest on.  Per new observation
+# the engine folds the conditional mean and variance of the likelihood over the draws in closed form (csrc/predict.h,
+# csrc/predict_kernel.h): the predicted probability / mean without the Monte Carlo noise of averaged replicates.
+PREDICT_REFUSED_FAMILIES = (ms.D_TRUNCNORMAL, ms.D_POTENTIAL, ms.D_DERIVED)
+
+
+def predict_refusal(spec, nodes=None) -> Optional[str]:
+    """Why conditional moments of `spec`'s observed `nodes` cannot be formed: `loglik.refusal`'s reasons, and the families
+    csrc/predict.h has no moments for."""
+    why = loglik.refusal(spec, nodes)
+    if why:
+        return why
+    for name, kind, index, _ in (ms.observed_nodes(spec) if nodes is None else nodes):
+        if kind == ms.LL_FACTOR and spec.factors[index].dist in PREDICT_REFUSED_FAMILIES:
+            return f"{name!r} is a {ms.DIST_NAMES[spec.factors[index].dist]} factor: conditional moments of that family are out of scope"
+    return None
+
+
+def predict_from_accumulators(mean_i, var_between_i, var_within_i, lpd_i, n_draws: int, pointwise: bool = True) -> dict:
+    """The predictions from the streamed state of S = `n_draws` pooled draws over M new observations: `mean` the posterior
+    predictive mean (the mean over the draws of the conditional mean), `var_between` the population variance over the draws of the
+    conditional mean, `var_within` the mean over the draws of the conditional variance, `sd` = sqrt(var_between + var_within) -- the
+    law of total variance for the empirical mixture of the draws.  With held-out values (`lpd_i` not None): lpd_i = log mean_s
+    p(y_i | theta_s), elpd = sum lpd_i and se = sqrt(M var(lpd_i)), the shape of `loglik.loo`'s result (`lpd_i` is dropped without
+    `pointwise`).  NaN and inf are not hidden."""
+    mean, vb, vw = (np.asarray(a, dtype="float64") for a in (mean_i, var_between_i, var_within_i))
+    M = int(mean.size)
+    with np.errstate(invalid="ignore"):
+        out = {"mean": mean, "var_between": vb, "var_within": vw, "sd": np.sqrt(vb + vw), "n_samples": int(n_draws), "n_data_points": M}
+    if lpd_i is not None:
+        lpd = np.asarray(lpd_i, dtype="float64")
+        with np.errstate(invalid="ignore"):
+            out["elpd"] = float(lpd.sum())
+            out["se"] = float(np.sqrt(M * np.var(lpd))) if M else float("nan")
+        if pointwise:
+            out["lpd_i"] = lpd
+    return out
+
+
+def predict(model, draws, new_data, *, var_name: Optional[str] = None, expected: bool = False, replicates: bool = False, random_seed=0,
+            chain_ids=None, pointwise: bool = True, device: Optional[int] = None) -> dict:
+    """Predictions of the fitted `model` at new data, streamed: `new_data` = {observed variable: dict of arrays} as
+    `model_spec.with_data` takes it (`model_spec.data_inputs(spec)` lists the keys).  One device function is built for the model at
+    the new rows and closed; the pooled draws stream by in chain order and the (draws x rows) matrix is never formed.  Returns
+    `predict_from_accumulators`'s dict for `var_name` (default: the one variable `new_data` names), arrays in the order the new
+    rows were passed; with held-out values (`y` / `observed` given) also lpd_i, elpd and se.
+
+    `expected=True` adds "expected" (chains, draws, M): the conditional mean per draw -- PyMC's `mu` / `p` Deterministic at the
+    new rows; credible intervals of the prediction come from it.  `replicates=True` adds "predictions" (chains, draws, M): one
+    replicate per draw, what `sample_posterior_predictive` draws for the model at the new rows (its refusals, `random_seed`,
+    `chain_ids` and global draw index)."""
+    spec = ms.with_data(loglik._spec_of(model), new_data)
+    if var_name is None:
+        if len(new_data) != 1:
+            raise TypeError(f"new_data names {sorted(new_data)}, var_name cannot be None")
+        var_name = next(iter(new_data))
+    node = loglik._select(spec, var_name)[0]
+    why = predict_refusal(spec, [node])
+    if why:
+        raise ValueError("predictions refused: " + why)
+    if replicates:
+        _nodes_or_refuse(spec, var_name)
+    name, kind, index, size = node
+    with_y = name not in spec.predict_no_y
+    q = loglik._draws_array(draws, spec.n)
+    ids = _chain_ids(draws, chain_ids, q.shape[0])
+    f, _ = loglik._function(spec, device, None)
+    try:
+        acc = f.pred_accumulator(name, with_y=with_y, node=(kind, index))
+        try:
+            for c in range(q.shape[0]):
+                acc.update(q[c])
+            mean_i, vb, vw, lpd_i, n_draws = acc.read()
+        finally:
+            acc.close()
+        cols = [loglik.caller_order(spec, kind, a) for a in (mean_i, vb, vw)]
+        out = predict_from_accumulators(*cols, loglik.caller_order(spec, kind, lpd_i) if with_y else None, n_draws, pointwise=pointwise)
+        if expected:
+            e = np.stack([f.predict_moments(name, q[c], node=(kind, index), var=False)[0] for c in range(q.shape[0])])
+            out["expected"] = loglik.caller_order(spec, kind, e)
+        if replicates:
+            y = np.stack([f.posterior_predictive(name, q[k], seed=random_seed, draw0=c * q.shape[1], node=(kind, index)) for k, c in enumerate(ids)])
+            out["predictions"] = loglik.caller_order(spec, kind, y)
+        return out
+    finally:
+        f.close()
+
+
 # ---- prior predictive ----------------------------------------------------------------------------------------------------------------
 # `pm.sample_prior_predictive` draws the free variables from their priors, then the data given them.  The first half is the engine's
 # `nuts_model_prior` (csrc/prior.h, csrc/prior_kernel.h): S unconstrained positions in ancestral order; the second half is the

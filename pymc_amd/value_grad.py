@@ -293,6 +293,27 @@ class DeviceValueGradFunction:
         kind, index = self._ll_node(name, node)
         return PpcAccumulator(self, kind, index, seed)
 
+    def predict_moments(self, name: str, q, node=None, var: bool = True):
+        """Conditional mean and variance of observed variable `name` per raveled unconstrained draw q [S, n] -> (mean [S, size],
+        var [S, size] or None) (`nuts_model_predict_moments`; logit rows in the spec's group-sorted order).  The function is that of
+        a spec carrying the rows to predict at (`model_spec.with_data`)."""
+        lib = _lib.load()
+        kind, index = self._ll_node(name, node)
+        q = np.ascontiguousarray(np.asarray(q, dtype="float64").reshape(-1, self.n))
+        size = C.c_int64()
+        _lib.check(lib.nuts_model_loglik_size(self._handle, kind, index, C.byref(size)), "nuts_model_loglik_size")
+        mean = np.empty((q.shape[0], size.value))
+        v = np.empty((q.shape[0], size.value)) if var else None
+        rc = lib.nuts_model_predict_moments(self._handle, kind, index, _lib.dptr(q), q.shape[0], _lib.dptr(mean), _lib.dptr(v) if var else None)
+        _lib.check(rc, "nuts_model_predict_moments")
+        return mean, v
+
+    def pred_accumulator(self, name: str, with_y: bool = True, node=None) -> "PredAccumulator":
+        """Device-resident streaming predictions of observed variable `name` (`nuts_pred_*`); `with_y`: the node's observed
+        values are held-out values, whose log predictive density is folded too."""
+        kind, index = self._ll_node(name, node)
+        return PredAccumulator(self, kind, index, with_y)
+
     def loo_pit_accumulator(self, psis_accumulator: "PsisAccumulator", seed: int = 0) -> "LooPitAccumulator":
         """Device-resident LOO predictive checks of the observed variable of `psis_accumulator`, which must hold all of its draws:
         the second pass over them (`nuts_loo_pit_*`)."""
@@ -455,6 +476,46 @@ class PpcAccumulator:
     def close(self):
         if getattr(self, "_handle", None):
             _lib.load().nuts_ppc_destroy(self._handle)
+            self._handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class PredAccumulator:
+    """`nuts_pred`: per observation Welford's (mean, M2) of the conditional mean, the running mean of the conditional variance and
+    the running log-sum-exp of the held-out log-density, updated by any number of `update(q [S, n])` calls in any split."""
+
+    def __init__(self, func: DeviceValueGradFunction, kind: int, index: int, with_y: bool = True):
+        lib = _lib.load()
+        self._func = func      # (the handle must not outlive its model)
+        size = C.c_int64()
+        _lib.check(lib.nuts_model_loglik_size(func._handle, kind, index, C.byref(size)), "nuts_model_loglik_size")
+        self.size = size.value
+        self.with_y = bool(with_y)
+        self._handle = lib.nuts_pred_create(func._handle, kind, index, int(self.with_y))
+        if not self._handle:
+            raise ValueError(f"nuts_pred_create: {_lib.last_error()}")
+
+    def update(self, q) -> None:
+        q = np.ascontiguousarray(np.asarray(q, dtype="float64").reshape(-1, self._func.n))
+        _lib.check(_lib.load().nuts_pred_update(self._handle, _lib.dptr(q), q.shape[0]), "nuts_pred_update")
+
+    def read(self):
+        """(mean_i, var_between_i = M2 / S, var_within_i, lpd_i or None, draws so far)"""
+        mean, vb, vw = (np.empty(self.size) for _ in range(3))
+        lpd = np.empty(self.size) if self.with_y else None
+        n = C.c_int64()
+        rc = _lib.load().nuts_pred_read(self._handle, _lib.dptr(mean), _lib.dptr(vb), _lib.dptr(vw), _lib.dptr(lpd) if self.with_y else None, C.byref(n))
+        _lib.check(rc, "nuts_pred_read")
+        return mean, vb, vw, lpd, n.value
+
+    def close(self):
+        if getattr(self, "_handle", None):
+            _lib.load().nuts_pred_destroy(self._handle)
             self._handle = None
 
     def __del__(self):
